@@ -17,6 +17,20 @@ Launch (driver contract):
 `ms_per_step` is the max-over-ranks time for the K steps of the
 co-located pair. Quota enforcement error (server-side, from gpu-schd's
 sliding-window accounting) is reported in config.quota_error_pct.
+
+A plain run sets up, warms up, times the K steps and prints the result
+line. `--dump-outputs DIR` additionally has every pod write what its
+last timed step computed (see bench_worker.dump_outputs). Inputs and
+initial weights are seeded per pod name, and with this option each pod
+rewinds its weights, BN buffers and momenta to that seeded state right
+before the last timed step: training from random init amplifies the
+ulp-level run-to-run noise of MIOpen's atomic weight-gradient kernels
+to percents within a few steps, whereas one step from fixed state is
+reproducible (conv weights, which those kernels update, stay out of
+the dump), so two builds can be compared file for file (and
+config.per_pod_loss is then the initial-state loss, about ln 1000).
+`--full` is where secondary measurements that need runs of their own
+belong; there are none today.
 """
 from __future__ import annotations
 
@@ -79,6 +93,25 @@ def main():
     # torch.optim.SGD on MI355X (same semantics, numerics-tested)
     ap.add_argument("--fused-sgd", action=argparse.BooleanOptionalAction,
                     default=True)
+    # the tuned MIOpen db shipped in kubeshare_amd/ops/miopen_udb already
+    # names the fastest solver for every flagship conv shape: measured
+    # 31.5 ms/step solo either way, but the exhaustive find costs ~60 s
+    # per pod at the first warmup step (~110 s for a co-located pair)
+    ap.add_argument("--miopen-find", action=argparse.BooleanOptionalAction,
+                    default=False,
+                    help="benchmark every MIOpen solver per conv shape "
+                         "during warmup; use it for a model or batch size "
+                         "the shipped tuned db does not cover")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what each pod's "
+                         "last timed step computed (loss, logits, a fixed "
+                         "seeded sample of the updated BN/fc parameters) as "
+                         "float32 DIR/pod<rank>-<i>.<name>.npy; that step "
+                         "starts from the seeded initial state")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the benchmark's secondary measurements; "
+                         "there are none today (the quota error comes from "
+                         "the timed run itself), so this changes nothing")
     args = ap.parse_args()
 
     import torch
@@ -128,7 +161,12 @@ def main():
                    "--device", wdev, "--dtype",
                    "bf16" if args.dtype == "bf16" else "fp32",
                    "--use-ops", args.use_ops] \
-                  + (["--fused-sgd"] if args.fused_sgd else [])
+                  + (["--fused-sgd"] if args.fused_sgd else []) \
+                  + ["--miopen-find" if args.miopen_find
+                     else "--no-miopen-find"]
+            if args.dump_outputs:
+                cmd += ["--dump-outputs", os.path.abspath(args.dump_outputs),
+                        "--dump-name", f"pod{local_rank}-{i}"]
             env["PYTHONPATH"] = REPO + os.pathsep + env.get("PYTHONPATH", "")
             p = subprocess.Popen(cmd, env=env, cwd=REPO,
                                  stdin=subprocess.PIPE,
@@ -172,6 +210,13 @@ def main():
         time.sleep(0.4)
         stats = share.stats()
         quota_err = _quota_error(st0, stats)
+
+        if args.dump_outputs:
+            for name, p in workers:
+                line = p.stdout.readline().strip()
+                if line != "DUMPED":
+                    raise RuntimeError(f"{name}: expected DUMPED, got "
+                                       f"{line!r} (exit={p.poll()})")
     finally:
         for _, p in workers:
             if p.poll() is None:
@@ -219,6 +264,7 @@ def main():
                 "pods_per_gpu": args.pods_per_gpu,
                 "gpu_request": args.request,
                 "gpu_limit": args.limit,
+                "miopen_find": args.miopen_find,
                 "quota_error_pct": round(mean_qerr, 3)
                                     if mean_qerr is not None else None,
                 "quota_error_per_pod": {k: round(v, 3)

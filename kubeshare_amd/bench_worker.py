@@ -5,6 +5,7 @@ Protocol with the parent (bench.py / tests):
     worker -> parent: READY\n                (after warmup + sync)
     parent -> worker: GO\n
     worker -> parent: DONE <elapsed_s> <images> <loss>\n
+    worker -> parent: DUMPED\n               (only with --dump-outputs)
 
 Run exactly --steps full training steps (forward + loss + backward +
 optimizer step) between GO and DONE; no work is skipped inside the
@@ -41,6 +42,37 @@ def check_hook_active(required: bool):
     return active
 
 
+PARAM_SAMPLE = 1 << 20  # at most this many parameter elements are dumped
+
+
+def dump_outputs(dump_dir: str, name: str, loss, logits, params):
+    """Write what the last timed step produced as <dir>/<name>.*.npy
+    (float32): its loss, its logits, and the parameters the optimizer
+    left behind, conv weights excepted (a fixed seeded sample if they
+    are more than PARAM_SAMPLE). That step starts from the seeded
+    initial state (see `rewind` in main), so the files depend on the
+    seeds and the kernels alone. Conv weights stay out because MIOpen's
+    tuned weight-gradient solvers accumulate with atomics: their result
+    differs by a bf16 ulp from run to run, while BN and fc parameters
+    (whose gradients come through every data-gradient, BN-backward and
+    GEMM kernel of the step) are bit-reproducible."""
+    import numpy as np
+    import torch
+
+    os.makedirs(dump_dir, exist_ok=True)
+    flat = torch.cat([p.detach().float().flatten() for p in params
+                      if p.dim() != 4])
+    if flat.numel() > PARAM_SAMPLE:
+        g = torch.Generator().manual_seed(0)
+        idx = torch.randperm(flat.numel(), generator=g)[:PARAM_SAMPLE]
+        flat = flat[idx.sort().values.to(flat.device)]
+    for key, t in (("loss", loss.detach().reshape(1)),
+                   ("logits", logits.detach()),
+                   ("params_sample", flat)):
+        np.save(os.path.join(dump_dir, f"{name}.{key}.npy"),
+                t.float().cpu().numpy())
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--model", default="resnet50",
@@ -60,6 +92,15 @@ def main():
                     help="use the kubeshare_amd HIP fused ops")
     ap.add_argument("--fused-sgd", action="store_true",
                     help="use the HIP multi-tensor SGD instead of torch's")
+    ap.add_argument("--miopen-find", action=argparse.BooleanOptionalAction,
+                    default=True,
+                    help="benchmark every MIOpen solver per conv shape at "
+                         "the first step (about a minute for ResNet50); "
+                         "off: take the solver the (tuned) find-db names")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after DONE, write the last timed step's outputs "
+                         "as DIR/<dump-name>.*.npy and print DUMPED")
+    ap.add_argument("--dump-name", default="pod")
     args = ap.parse_args()
 
     from kubeshare_amd.utils.tuning import apply_miopen_tuning
@@ -67,7 +108,8 @@ def main():
 
     import torch
 
-    torch.backends.cudnn.benchmark = True  # MIOpen find+cache per shape
+    # MIOpen find+cache per shape, or immediate mode off the find-db
+    torch.backends.cudnn.benchmark = args.miopen_find
     dev = torch.device(args.device)
     on_gpu = dev.type == "cuda"
     if on_gpu:
@@ -113,6 +155,27 @@ def main():
     y = torch.randint(0, 1000, (args.batch,), device=dev)
 
     amp_dtype = torch.bfloat16 if args.dtype == "bf16" else None
+    last = {}  # the latest step's logits, kept for --dump-outputs
+
+    # MIOpen's tuned weight-gradient solvers accumulate with atomics, so
+    # two runs differ by a bf16 ulp in some gradients after one step and
+    # training from random init amplifies that to percents within 25
+    # steps. For the dumped step to be a function of the seeds alone,
+    # --dump-outputs rewinds parameters, BN buffers and momenta (in
+    # place: captured graphs stay valid) to their seeded initial values
+    # right before the last timed step.
+    rewind = None
+    if args.dump_outputs:
+        state = [p.data for p in model.parameters()] + list(model.buffers())
+        initial = [t.clone() for t in state]
+
+        def rewind():
+            torch._foreach_copy_(state, initial)
+            momenta = opt.momenta if hasattr(opt, "momenta") else [
+                st["momentum_buffer"] for st in opt.state.values()
+                if st.get("momentum_buffer") is not None]
+            if momenta:
+                torch._foreach_zero_(momenta)
 
     def step():
         opt.zero_grad(set_to_none=True)
@@ -125,6 +188,7 @@ def main():
             loss = loss_fn(out, y)
         loss.backward()
         opt.step()
+        last["logits"] = out
         return loss
 
     for _ in range(args.warmup):
@@ -141,7 +205,9 @@ def main():
         return 1
 
     t0 = time.perf_counter()
-    for _ in range(args.steps):
+    for i in range(args.steps):
+        if rewind is not None and i == args.steps - 1:
+            rewind()
         loss = step()
     if on_gpu:
         torch.cuda.synchronize()
@@ -149,6 +215,10 @@ def main():
 
     images = args.steps * args.batch
     print(f"DONE {t1 - t0:.6f} {images} {loss.item():.4f}", flush=True)
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, args.dump_name, loss,
+                     last["logits"], list(model.parameters()))
+        print("DUMPED", flush=True)
     return 0
 
 

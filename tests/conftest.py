@@ -47,3 +47,18 @@ def native_bins():
         subprocess.run(["make", "-C", NATIVE], check=True,
                        capture_output=True)
     return {t: _built(t) for t in targets}
+
+
+@pytest.fixture
+def short_workdir():
+    """A scratch directory whose path is short. A Unix socket path holds
+    at most 107 bytes (sockaddr_un.sun_path), which a socket below
+    pytest's tmp_path exceeds when the temporary directory itself lies
+    deep (production uses /kubeshare)."""
+    import tempfile
+    base = min({tempfile.gettempdir(), "/tmp"}, key=len)
+    d = tempfile.mkdtemp(prefix="ks-", dir=base)
+    try:
+        yield d
+    finally:
+        shutil.rmtree(d, ignore_errors=True)

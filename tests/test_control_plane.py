@@ -439,17 +439,19 @@ def test_launcher_pod_churn(tmp_path, native_bins, fake_gpus):
         nd.stop()
 
 
-def test_pod_mgr_uds_default_transport(tmp_path, native_bins, fake_gpus):
+def test_pod_mgr_uds_default_transport(short_workdir, native_bins,
+                                       fake_gpus):
     """pod-mgr listens on BOTH the per-pod UDS (default transport, no
     hostNetwork, unreachable cross-pod) and the TCP fallback; a token
     round-trips over each."""
     from kubeshare_amd.isolation.local import free_port
     base_port = free_port()
-    nd = NodeDaemon(str(tmp_path), base_port=base_port, base_quota=40,
+    nd = NodeDaemon(short_workdir, base_port=base_port, base_quota=40,
                     min_quota=10, window=2000, gpus=fake_gpus)
     nd.start()
     mgr_port = free_port()
     uds = C.pod_manager_uds(mgr_port, nd.sock_dir)
+    assert len(os.fsencode(uds)) <= 107, f"socket path too long: {uds}"
     try:
         ConfigDaemon("node-a", nd.config_dir, nd.port_dir).update(
             [PodDemand("ns", "udsy", "u1", "node-a", "GPU-fake-0",
@@ -486,13 +488,12 @@ def test_simulator_reference_trace_full():
     """The reference's actual 989-job arrival trace
     (test/simulator/trace.txt) replayed end to end against the
     in-memory pipeline — the load test the reference could only run on
-    a live lab cluster. Skipped when the reference checkout is absent."""
+    a live lab cluster. The trace is stored as a fixture under
+    tests/golden/."""
     import subprocess
     import sys as _sys
-    trace = "/root/reference/test/simulator/trace.txt"
-    if not os.path.exists(trace):
-        pytest.skip("reference trace not available")
     repo = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    trace = os.path.join(repo, "tests", "golden", "simulator_trace.txt")
     r = subprocess.run(
         [_sys.executable, "tools/simulator.py", "--trace", trace,
          "--nodes", "4"],

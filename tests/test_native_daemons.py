@@ -373,12 +373,13 @@ def test_non_gang_waits_for_gang_drain(native_bins, tmp_path):
         schd.stop()
 
 
-def test_unix_domain_socket_chain(native_bins, tmp_path):
+def test_unix_domain_socket_chain(native_bins, tmp_path, short_workdir):
     """gpu-schd on a Unix socket + pod-mgr bridging UDS upstream to a
     TCP client port — the no-hostNetwork deployment mode (SURVEY.md §5:
     prefer UDS through the shared hostPath)."""
     cfg = _write_config(tmp_path, [("ns/u1", 1.0, 0.5, 0)])
-    uds = str(tmp_path / "schd.sock")
+    uds = os.path.join(short_workdir, "schd.sock")
+    assert len(os.fsencode(uds)) <= 107, f"socket path too long: {uds}"
     schd = subprocess.Popen(
         [native_bins["gpu-schd"], "-p", cfg, "-f", "GPU-x",
          "-U", uds, "-q", "60", "-m", "10", "-w", "2000"],

@@ -5,7 +5,7 @@ format against the in-memory harness, so the full QueueSort->Permit
 pipeline is load-tested in CI with no cluster).
 
     python tools/simulator.py --jobs 500 --nodes 4
-    python tools/simulator.py --trace /root/reference/test/simulator/trace.txt
+    python tools/simulator.py --trace tests/golden/simulator_trace.txt
 """
 import argparse
 import json
