@@ -4,6 +4,8 @@ as blocks so kubeshare_amd.ops.fuse_model can route them through the
 fused NHWC bf16 BN+ReLU gfx950 kernel (same op the ResNet blocks use)."""
 import torch.nn as nn
 
+from .pool import FusedMaxPool2d
+
 _CFG16 = [64, 64, "M", 128, 128, "M", 256, 256, 256, "M",
           512, 512, 512, "M", 512, 512, 512, "M"]
 
@@ -30,7 +32,7 @@ class VGG(nn.Module):
         layers, in_ch = [], 3
         for v in cfg:
             if v == "M":
-                layers.append(nn.MaxPool2d(2, 2))
+                layers.append(FusedMaxPool2d(2, 2))
             else:
                 layers.append(ConvBNReLU(in_ch, v))
                 in_ch = v

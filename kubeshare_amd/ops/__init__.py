@@ -12,7 +12,8 @@ import os
 _HERE = os.path.dirname(os.path.abspath(__file__))
 _BUILD_DIR = os.path.join(_HERE, "_build")
 _SRCS = [os.path.join(_HERE, "hip", "ks_ops.hip"),
-         os.path.join(_HERE, "hip", "bn_relu.hip")]
+         os.path.join(_HERE, "hip", "bn_relu.hip"),
+         os.path.join(_HERE, "hip", "pool.hip")]
 
 _ext = None
 
@@ -259,9 +260,114 @@ def bn_relu(x, bn, res=None, relu=True):
                     bn.running_var, bn.training, bn.momentum, bn.eps, relu)
 
 
+# ------------------------------------------------------ fused max-pool
+_POOL_CONFIGS = ((3, 2, 1), (2, 2, 0))  # (k, s, p) compiled in pool.hip
+_MaxPoolNHWCFn = None
+
+
+def _pool_int(v):
+    if type(v) is int:
+        return v
+    if isinstance(v, (tuple, list)) and len(v) == 2 and v[0] == v[1] \
+            and type(v[0]) is int:
+        return v[0]
+    return None
+
+
+def _pool_cfg(kernel_size, stride, padding):
+    """(k, s, p) as ints; None entries for non-square / non-int
+    arguments (never equal to a compiled configuration)."""
+    if stride is None or stride == () or stride == []:
+        stride = kernel_size
+    return (_pool_int(kernel_size), _pool_int(stride), _pool_int(padding))
+
+
+def _pool_cfg_supported(x, cfg) -> bool:
+    import torch
+
+    if cfg not in _POOL_CONFIGS or x.dim() != 4:
+        return False
+    n, c, h, w = x.shape
+    k, _, p = cfg
+    return (x.is_cuda and x.dtype == torch.bfloat16
+            and c % 8 == 0 and 8 <= c <= 2048 and n >= 1
+            and h + 2 * p >= k and w + 2 * p >= k
+            and n * h * w < 2 ** 31
+            and x.is_contiguous(memory_format=torch.channels_last))
+
+
+def fused_pool_enabled() -> bool:
+    """KUBESHARE_FUSED_POOL=0 keeps flagged pool modules on the stock
+    path (A/B runs, operator escape hatch)."""
+    return os.environ.get("KUBESHARE_FUSED_POOL", "1") != "0"
+
+
+def max_pool_supported(x, kernel_size, stride=None, padding=0) -> bool:
+    """True when pool.hip covers the call: (k, s, p) in (3, 2, 1) /
+    (2, 2, 0), channels-last bf16 on the GPU, C % 8 == 0, C <= 2048 (one
+    256-thread block spans a pixel's channel groups), a non-empty output
+    and N*H*W below 2**31 (pixel indices are 32-bit, element offsets
+    64-bit)."""
+    return _pool_cfg_supported(x, _pool_cfg(kernel_size, stride, padding))
+
+
+def _max_pool_autograd():
+    """Lazily build the autograd.Function (torch import deferred)."""
+    global _MaxPoolNHWCFn
+    if _MaxPoolNHWCFn is not None:
+        return _MaxPoolNHWCFn
+    import torch
+    from torch.autograd.function import once_differentiable
+
+    class MaxPoolNHWCFn(torch.autograd.Function):
+        """NHWC bf16 max-pool via hip/pool.hip. The forward stores a
+        one-byte window-local argmax per output element and autograd
+        keeps ONLY that (not the pool input); the backward gathers, so
+        it needs no memset of dx and no atomics."""
+
+        @staticmethod
+        def forward(ctx, x, k, s, p, want_idx):
+            out = _load().max_pool_nhwc_fwd(x, k, s, p, want_idx)
+            if want_idx:
+                ctx.save_for_backward(out[1])
+                ctx.input_sizes = list(x.shape)
+                ctx.cfg = (k, s, p)
+            return out[0]
+
+        @staticmethod
+        @once_differentiable
+        def backward(ctx, dy):
+            (idx,) = ctx.saved_tensors
+            # y.sum().backward() hands over a stride-0 expanded dy
+            if not dy.is_contiguous(memory_format=torch.channels_last):
+                dy = dy.contiguous(memory_format=torch.channels_last)
+            k, s, p = ctx.cfg
+            dx = _load().max_pool_nhwc_bwd(dy, idx, ctx.input_sizes,
+                                           k, s, p)
+            return dx, None, None, None, None
+
+    _MaxPoolNHWCFn = MaxPoolNHWCFn
+    return MaxPoolNHWCFn
+
+
+def max_pool_nhwc(x, kernel_size, stride=None, padding=0):
+    """Max-pool through the gfx950 kernels in hip/pool.hip; falls back
+    to eager F.max_pool2d for anything max_pool_supported rejects."""
+    import torch
+
+    cfg = _pool_cfg(kernel_size, stride, padding)
+    if not _pool_cfg_supported(x, cfg):
+        return torch.nn.functional.max_pool2d(x, kernel_size, stride,
+                                              padding)
+    want_idx = torch.is_grad_enabled() and x.requires_grad
+    fn = _MaxPoolNHWCFn or _max_pool_autograd()
+    return fn.apply(x, *cfg, want_idx)
+
+
 def fuse_model(model):
-    """Enable the fused BN+ReLU(+add) path on kubeshare_amd models
-    (ResNet blocks check their `fused_ops` flag); verifies the extension
+    """Enable the fused BN+ReLU(+add) and max-pool paths on
+    kubeshare_amd models (blocks and pool modules check their
+    `fused_ops` flag); verifies the extension
     is importable first (fail-loud on GPU boxes)."""
     _load()
     for m in model.modules():

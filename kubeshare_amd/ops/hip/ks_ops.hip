@@ -11,6 +11,8 @@
 //  - multi-tensor SGD+momentum: one launch per dtype-bucket chunk set,
 //    grid-stride, float4/bf16x8-vectorized (guide G13: vectorize ANY
 //    memory-bound op; scalar bf16 ~2-2.5x slower).
+//  - bn_relu.hip / pool.hip: fused NHWC bf16 BN+ReLU(+add) and max-pool
+//    (bound below).
 #include <hip/hip_runtime.h>
 #include <torch/extension.h>
 #include <ATen/cuda/CUDAContext.h>
@@ -133,6 +135,14 @@ std::vector<torch::Tensor> bn_relu_bwd(torch::Tensor x, torch::Tensor y,
                                        torch::Tensor invstd, bool need_dres,
                                        bool relu);
 
+// fused NHWC bf16 max-pool, one-byte argmax + gather backward (pool.hip)
+std::vector<torch::Tensor> max_pool_nhwc_fwd(torch::Tensor x, int64_t k,
+                                             int64_t s, int64_t p,
+                                             bool want_idx);
+torch::Tensor max_pool_nhwc_bwd(torch::Tensor dy, torch::Tensor idx,
+                                std::vector<int64_t> input_sizes, int64_t k,
+                                int64_t s, int64_t p);
+
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("burn", &burn, "occupy the GPU for ~ms milliseconds",
         py::arg("ms"), py::arg("blocks") = 1024, py::arg("threads") = 256);
@@ -141,4 +151,6 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("bn_relu_fwd_train", &bn_relu_fwd_train);
   m.def("bn_relu_fwd_eval", &bn_relu_fwd_eval);
   m.def("bn_relu_bwd", &bn_relu_bwd);
+  m.def("max_pool_nhwc_fwd", &max_pool_nhwc_fwd);
+  m.def("max_pool_nhwc_bwd", &max_pool_nhwc_bwd);
 }
