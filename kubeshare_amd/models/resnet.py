@@ -38,20 +38,28 @@ class Bottleneck(nn.Module):
             )
 
     def forward(self, x):
+        # a pair (x, x_id) is one activation under two autograd handles
+        # (ops.bn_relu(fork=True)): conv1 consumes x, the identity /
+        # downsample branch x_id, and a pair comes back. A plain tensor
+        # in gives a plain tensor out.
+        pair = isinstance(x, tuple)
+        x, x_id = x if pair else (x, x)
         if self.fused_ops:
             from .. import ops
             # downsample BN has no activation: fused no-ReLU variant
             # (otherwise it falls back to MIOpen's fp32 spatial BN)
-            identity = x if self.down is None else \
-                ops.bn_relu(self.down[0](x), self.down[1], relu=False)
+            identity = x_id if self.down is None else \
+                ops.bn_relu(self.down[0](x_id), self.down[1], relu=False)
             out = ops.bn_relu(self.conv1(x), self.bn1)
             out = ops.bn_relu(self.conv2(out), self.bn2)
-            return ops.bn_relu(self.conv3(out), self.bn3, res=identity)
-        identity = x if self.down is None else self.down(x)
+            return ops.bn_relu(self.conv3(out), self.bn3, res=identity,
+                               fork=pair)
+        identity = x_id if self.down is None else self.down(x_id)
         out = self.relu(self.bn1(self.conv1(x)))
         out = self.relu(self.bn2(self.conv2(out)))
         out = self.bn3(self.conv3(out))
-        return self.relu(out + identity)
+        out = self.relu(out + identity)
+        return (out, out) if pair else out
 
 
 class BasicBlock(nn.Module):
@@ -74,16 +82,20 @@ class BasicBlock(nn.Module):
             )
 
     def forward(self, x):
+        pair = isinstance(x, tuple)  # see Bottleneck.forward
+        x, x_id = x if pair else (x, x)
         if self.fused_ops:
             from .. import ops
-            identity = x if self.down is None else \
-                ops.bn_relu(self.down[0](x), self.down[1], relu=False)
+            identity = x_id if self.down is None else \
+                ops.bn_relu(self.down[0](x_id), self.down[1], relu=False)
             out = ops.bn_relu(self.conv1(x), self.bn1)
-            return ops.bn_relu(self.conv2(out), self.bn2, res=identity)
-        identity = x if self.down is None else self.down(x)
+            return ops.bn_relu(self.conv2(out), self.bn2, res=identity,
+                               fork=pair)
+        identity = x_id if self.down is None else self.down(x_id)
         out = self.relu(self.bn1(self.conv1(x)))
         out = self.bn2(self.conv2(out))
-        return self.relu(out + identity)
+        out = self.relu(out + identity)
+        return (out, out) if pair else out
 
 
 class ResNet(nn.Module):
@@ -120,9 +132,16 @@ class ResNet(nn.Module):
         if self.fused_ops:
             from .. import ops
             x = self.maxpool(ops.bn_relu(self.conv1(x), self.bn1))
+            if ops.bn_fork_enabled():
+                # every block hands its output on as a pair, so the two
+                # gradients of a residual join reach the block's last BN
+                # separately and are summed inside its backward kernel
+                x = (x, x)
         else:
             x = self.maxpool(self.relu(self.bn1(self.conv1(x))))
         x = self.layer4(self.layer3(self.layer2(self.layer1(x))))
+        if isinstance(x, tuple):
+            x = x[0]
         x = torch.flatten(self.avgpool(x), 1)
         return self.fc(x)
 

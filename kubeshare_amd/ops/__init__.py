@@ -70,15 +70,23 @@ class FusedSGD:
     """Multi-tensor fused SGD+momentum (f32 master params).
 
     Matches torch.optim.SGD(momentum=mu, weight_decay=wd, dampening=0,
-    nesterov=False) semantics; one kernel per tensor, no Python-side
-    per-parameter loop allocations after the first step.
+    nesterov=False) semantics. step() hands every (param, grad, momentum)
+    triple to ONE multi-tensor kernel launch per 110 tensors (ResNet50:
+    161 tensors, 2 launches); pointers travel in the kernel arguments,
+    so nothing requires the gradients to stay at the same address.
 
-    graph_mode="auto" (default on CUDA): once the grad set is stable,
-    the ~161 per-tensor update launches and the ~161 grad-zero memsets
-    are captured into two hipGraphs and replayed as ONE gated dispatch
-    each per step. Requires stable grad storage, so zero_grad() zeroes
-    in place instead of dropping the tensors (backward then accumulates
-    into the same buffers — pointer-stable, capture-safe).
+    zero_grad() therefore just drops the gradients (no kernels): the
+    next backward pass adopts its freshly computed gradient tensors
+    instead of running one fill and one `grad += new` kernel per
+    parameter.
+
+    graph_mode="auto" (default on CUDA): the one- or two-node step is
+    still captured into a hipGraph after the first full eager step, and
+    replayed only while every parameter, gradient and momentum pointer
+    equals the captured one; any other step launches eagerly.
+
+    KUBESHARE_SGD_MULTI=0 selects the per-tensor kernel (one launch per
+    tensor) for A/B runs; KUBESHARE_SGD_GRAPH=0 disables the capture.
     """
 
     def __init__(self, params, lr: float, momentum: float = 0.9,
@@ -92,63 +100,42 @@ class FusedSGD:
         # momentum buffers share the parameter's layout (channels-last
         # conv weights included): the kernel updates flat dense storage
         self.momenta = [torch.zeros_like(p) for p in self.params]
-        self._first = True
         self._graph_mode = graph_mode
+        self._multi = os.environ.get("KUBESHARE_SGD_MULTI", "1") != "0"
         self._step_graph = None
-        self._zero_graph = None
-        self._graph_ptrs = None  # grad data_ptrs the graphs were baked on
+        self._graph_ptrs = None  # data_ptrs the graph was baked on
 
     def _graphable(self):
         import torch
         if self._graph_mode == "off" or not torch.cuda.is_available():
             return False
-        import os
         if os.environ.get("KUBESHARE_SGD_GRAPH", "1") == "0":
             return False
         return all(p.grad is not None and p.grad.is_cuda
                    for p in self.params)
 
+    def _ptrs(self):
+        """Every address a captured step would touch; a replay is valid
+        only while all of them are what they were at capture."""
+        return tuple(
+            (p.data_ptr(), v.data_ptr(),
+             p.grad.data_ptr() if p.grad is not None else 0)
+            for p, v in zip(self.params, self.momenta))
+
     def zero_grad(self, set_to_none: bool = True):
-        if self._zero_graph is not None and self._graph_ptrs == tuple(
-                p.grad.data_ptr() if p.grad is not None else 0
-                for p in self.params):
-            self._zero_graph.replay()
-            return
         for p in self.params:
-            if p.grad is not None:
-                if set_to_none and self._step_graph is None:
-                    p.grad = None
-                else:
-                    # graph mode needs pointer-stable grads
-                    p.grad.zero_()
+            if set_to_none:
+                p.grad = None
+            elif p.grad is not None:
+                p.grad.zero_()
 
-    def _capture(self):
-        import torch
+    def _launch(self):
         ext = _load()
-        ps = [p.data for p in self.params]
-        gs = [p.grad for p in self.params]
-        vs = list(self.momenta)
-        ptrs = tuple(g.data_ptr() for g in gs)
-        # (the update kernel is already warm: capture happens right
-        # after a full eager step)
-        step_g = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(step_g):
-            ext.sgd_momentum_(ps, gs, vs, self.lr, self.momentum,
-                              self.weight_decay)
-        zero_g = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(zero_g):
-            for g in gs:
-                g.zero_()
-        self._step_graph = step_g
-        self._zero_graph = zero_g
-        self._graph_ptrs = ptrs
-
-    def step(self):
-        ext = _load()
-        if self._step_graph is not None and self._graph_ptrs == tuple(
-                p.grad.data_ptr() if p.grad is not None else 0
-                for p in self.params):
-            self._step_graph.replay()
+        if self._multi:
+            ext.sgd_momentum_multi_(
+                [p.data for p in self.params],
+                [p.grad for p in self.params], self.momenta,
+                self.lr, self.momentum, self.weight_decay)
             return
         ps, gs, vs = [], [], []
         for p, v in zip(self.params, self.momenta):
@@ -157,16 +144,32 @@ class FusedSGD:
             ps.append(p.data)
             gs.append(p.grad)
             vs.append(v)
-        if self._first:
-            # torch SGD's first step sets v = g + wd*p (no mu*v term
-            # since v starts at 0) — identical here because v==0.
-            self._first = False
         ext.sgd_momentum_(ps, gs, vs, self.lr, self.momentum,
                           self.weight_decay)
-        # after a full-set eager step with stable grads, capture the
-        # graphs for subsequent steps
+
+    def _capture(self):
+        import torch
+        ptrs = self._ptrs()
+        # (the update kernel is already warm: capture happens right
+        # after a full eager step)
+        step_g = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(step_g):
+            self._launch()
+        self._step_graph = step_g
+        self._graph_ptrs = ptrs
+
+    def step(self):
+        # torch SGD's first step sets v = g + wd*p (no mu*v term since v
+        # starts at 0) — identical here because v == 0.
+        if self._step_graph is not None and \
+                self._graph_ptrs == self._ptrs():
+            self._step_graph.replay()
+            return
+        self._launch()
+        # after a full-set eager step, capture the graph; it serves the
+        # later steps whose gradients land at the same addresses
         if self._step_graph is None and self._graph_mode == "auto" and \
-                len(gs) == len(self.params) and self._graphable():
+                self._graphable():
             try:
                 self._capture()
             except Exception:  # noqa: BLE001 — capture is an optimization
@@ -187,42 +190,56 @@ def _bn_relu_autograd():
         8-pass backward (incl. separate ReLU and residual-add kernels)
         with 3 forward passes and 5 (non-residual, mask recomputed
         from x) / 7 (residual, dym reuse) backward passes — see
-        profiles/README.md for the motivation."""
+        profiles/README.md for the motivation.
+
+        fork=True returns the pair (y, y2) with y2 = y.view_as(y): the
+        same memory under two autograd edges, one per consumer of a
+        residual join (the next block's conv1 and its identity branch).
+        The backward then receives the two gradients separately and the
+        stats kernel sums them in registers, instead of autograd running
+        a separate bf16 add kernel whose result that kernel re-reads.
+        Nothing on the fused path writes in place into y or y2; an
+        in-place op on either would corrupt the other consumer's input,
+        so keep it that way."""
 
         @staticmethod
         def forward(ctx, x, res, weight, bias, running_mean, running_var,
-                    training, momentum, eps, relu):
+                    training, momentum, eps, relu, fork=False):
             ext = _load()
             w32 = weight.float()
             b32 = bias.float()
+            # backward takes undefined gradients as None (a forked
+            # output may have no consumer) instead of zero tensors
+            ctx.set_materialize_grads(False)
+            ctx.with_res = res is not None
+            ctx.relu = relu
+            ctx.wdtype = weight.dtype
             if training:
                 y, mean, invstd = ext.bn_relu_fwd_train(
                     x, w32, b32, running_mean, running_var, momentum, eps,
                     res, relu)
                 ctx.save_for_backward(x, y, w32, b32, mean, invstd)
-                ctx.with_res = res is not None
-                ctx.relu = relu
-                ctx.wdtype = weight.dtype
-                return y
-            y = ext.bn_relu_fwd_eval(x, w32, b32, running_mean.float(),
-                                     running_var.float(), eps, res, relu)
-            ctx.save_for_backward(x, y, w32, b32, running_mean.float(),
-                                  (running_var.float() + eps).rsqrt())
-            ctx.with_res = res is not None
-            ctx.relu = relu
-            ctx.wdtype = weight.dtype
-            return y
+            else:
+                y = ext.bn_relu_fwd_eval(x, w32, b32, running_mean.float(),
+                                         running_var.float(), eps, res, relu)
+                ctx.save_for_backward(x, y, w32, b32, running_mean.float(),
+                                      (running_var.float() + eps).rsqrt())
+            return (y, y.view_as(y)) if fork else y
 
         @staticmethod
-        def backward(ctx, dy):
+        def backward(ctx, dy, dy2=None):
             ext = _load()
             x, y, w32, b32, mean, invstd = ctx.saved_tensors
+            if dy is None:
+                dy, dy2 = dy2, None
+            if dy is None:  # no gradient reached either output
+                return (None,) * 11
             out = ext.bn_relu_bwd(x, y, dy, w32, b32, mean, invstd,
-                                  ctx.with_res, ctx.relu)
+                                  ctx.with_res, ctx.relu, dy2)
             dx, dscale, dbias = out[0], out[1], out[2]
             dres = out[3] if ctx.with_res else None
             return (dx, dres, dscale.to(ctx.wdtype), dbias.to(ctx.wdtype),
-                    None, None, None, None, None, None)
+                    None, None, None, None, None, None, None)
 
     _BNReLUFn = BNReLUFn
     return BNReLUFn
@@ -231,11 +248,21 @@ def _bn_relu_autograd():
 _BNReLUFn = None
 
 
-def bn_relu(x, bn, res=None, relu=True):
+def bn_fork_enabled() -> bool:
+    """KUBESHARE_BN_FORK=0 keeps the residual joins unforked (autograd
+    sums the two gradients with its own add kernel); A/B runs, operator
+    escape hatch."""
+    return os.environ.get("KUBESHARE_BN_FORK", "1") != "0"
+
+
+def bn_relu(x, bn, res=None, relu=True, fork=False):
     """Fused BN[+ReLU][+residual add] using an nn.BatchNorm2d's
     parameters/buffers; relu=False serves activation-free BNs (the
     ResNet downsample path). Falls back to eager for shapes the kernel
-    does not cover (non-bf16, C%8!=0, not channels-last)."""
+    does not cover (non-bf16, C%8!=0, not channels-last).
+
+    fork=True returns the pair (y, y2), one handle per consumer of a
+    residual join (see BNReLUFn); the eager fall-back returns (y, y)."""
     import torch
 
     supported = (x.dtype == torch.bfloat16 and x.size(1) % 8 == 0
@@ -251,13 +278,15 @@ def bn_relu(x, bn, res=None, relu=True):
             bn.training, bn.momentum, bn.eps)
         if res is not None:
             y = y + res
-        return torch.relu(y) if relu else y
+        y = torch.relu(y) if relu else y
+        return (y, y) if fork else y
     if res is not None and not res.is_contiguous(
             memory_format=torch.channels_last):
         res = res.contiguous(memory_format=torch.channels_last)
     fn = _bn_relu_autograd()
     return fn.apply(x, res, bn.weight, bn.bias, bn.running_mean,
-                    bn.running_var, bn.training, bn.momentum, bn.eps, relu)
+                    bn.running_var, bn.training, bn.momentum, bn.eps, relu,
+                    fork)
 
 
 # ------------------------------------------------------ fused max-pool

@@ -4,8 +4,12 @@
 // MIOpen's spatial BN kernels + separate ReLU/add elementwise passes
 // are ~48% of the non-conv GPU time of a ResNet50 training step. The
 // stock path makes 5 full passes over the activation in forward and 8
-// in backward; these kernels make 3 and 7, and fold the residual add
-// and its gradient for free.
+// in backward; these kernels make 3 forward and 5 (non-residual) / 7
+// (residual) backward, and fold the residual add and its gradient for
+// free. Where the output of a residual BN feeds two consumers, the
+// backward also takes their two gradients separately and sums them in
+// registers (one extra read, 7+1 passes) instead of autograd's separate
+// bf16 add kernel (three passes) — see bn_bwd_stats_kernel.
 //
 // Design (cdna_hip_programming.md G13 vectorize, G7 ILP, G11 grid):
 //  - channels-last bf16, C % 8 == 0: one lane owns 8 CONSECUTIVE
@@ -51,6 +55,9 @@ __device__ __forceinline__ unsigned short f32_to_bf16(float f) {
 #define KS_BN_BLOCK 512
 #define KS_BN_UNROLL 4
 #define KS_BN_UNROLL_STATS 8
+// two-gradient bwd stats: rows loaded per sub-batch of a KS_BN_UNROLL
+// group (see bn_bwd_stats_kernel)
+#define KS_BN_UNROLL_DY2 2
 
 // ------------------------------------------------------------- fwd stats
 // Block partials: sum_part[b*C + c], sq_part[(B + b)*C + c].
@@ -249,10 +256,43 @@ __global__ void bn_apply_relu_kernel(const ushort8* __restrict__ x,
 // --------------------------------------------------------- bwd stats
 // dym = dy * (y > 0); dbias[c] = sum(dym); dscale[c] = sum(dym*xhat);
 // optionally writes dym (= the residual branch's gradient).
-template <bool WRITE_DYM>
+// WITH_DY2: y fed two consumers (the next block's conv1 and its identity
+// branch) and their gradients arrive separately; the join sum
+// bf16(f32(dy) + f32(dy2)) is formed in registers — bit-for-bit what a
+// separate bf16 add kernel would have written and this kernel re-read.
+__device__ __forceinline__ float bn_join_grad(unsigned short a,
+                                              unsigned short b) {
+  return bf16_to_f32(f32_to_bf16(bf16_to_f32(a) + bf16_to_f32(b)));
+}
+
+// dscale accumulation, pinned. Left to -ffp-contract the backend fused
+// `ads += g * xhat` for some channels and rows and not for others (it
+// vectorises across rows for channels 6 and 7 of a four-row group), so
+// the sums depended on the unroll. The pattern is now explicit and is
+// the one every earlier build computed: within a whole group of four
+// rows channels 0-5 use an FMA and channels 6-7 a rounded product, then
+// an add; the leftover rows use an FMA for every channel. Any unroll
+// that keeps a lane's rows in order and in the same groups of four
+// therefore gives the same bits.
+__device__ __forceinline__ float bn_mul_add_unfused(float acc, float a,
+                                                    float b) {
+#pragma clang fp contract(off)
+  float prod = a * b;
+  return acc + prod;
+}
+
+template <bool GROUPED>
+__device__ __forceinline__ float bn_acc_dscale(float acc, float g, float xhat,
+                                               int j) {
+  return (GROUPED && j >= 6) ? bn_mul_add_unfused(acc, g, xhat)
+                             : fmaf(g, xhat, acc);
+}
+
+template <bool WRITE_DYM, bool WITH_DY2 = false>
 __global__ void bn_bwd_stats_kernel(const ushort8* __restrict__ x,
                                     const ushort8* __restrict__ y,
                                     const ushort8* __restrict__ dy,
+                                    const ushort8* __restrict__ dy2,
                                     ushort8* __restrict__ dym_out,
                                     const float* __restrict__ mean,
                                     const float* __restrict__ invstd,
@@ -273,42 +313,60 @@ __global__ void bn_bwd_stats_kernel(const ushort8* __restrict__ x,
   }
   float8 adb = {0, 0, 0, 0, 0, 0, 0, 0};
   float8 ads = {0, 0, 0, 0, 0, 0, 0, 0};
+  // Rows advance in groups of KS_BN_UNROLL; a group is loaded U rows at
+  // a time. The two-gradient variant reads four tensors per row instead
+  // of three, and at U = KS_BN_UNROLL it spills (112 B/lane of scratch
+  // under the 128-VGPR budget); two rows at a time it does not.
+  constexpr int U = WITH_DY2 ? KS_BN_UNROLL_DY2 : KS_BN_UNROLL;
+  static_assert(KS_BN_UNROLL % U == 0, "sub-batches must tile a group");
   long long row = active ? (long long)blockIdx.x * rows_per_blk + roff : M;
   for (; row + (KS_BN_UNROLL - 1) * stride < M;
        row += KS_BN_UNROLL * stride) {
-    ushort8 xv[KS_BN_UNROLL], yv[KS_BN_UNROLL], gv[KS_BN_UNROLL];
-    long long k[KS_BN_UNROLL];
+    // a real loop: unrolled, the scheduler hoists the next sub-batch's
+    // loads over this one's arithmetic and the spill is back
+#pragma unroll 1
+    for (int h = 0; h < KS_BN_UNROLL; h += U) {
+      ushort8 xv[U], yv[U], gv[U];
+      ushort8 g2[U];
+      long long k[U];
 #pragma unroll
-    for (int u = 0; u < KS_BN_UNROLL; u++) {
-      k[u] = (row + u * stride) * CG + cg;
-      xv[u] = x[k[u]];
-      yv[u] = y[k[u]];
-      gv[u] = dy[k[u]];
-    }
-#pragma unroll
-    for (int u = 0; u < KS_BN_UNROLL; u++) {
-      ushort8 dm;
-#pragma unroll
-      for (int j = 0; j < 8; j++) {
-        float g = bf16_to_f32(yv[u][j]) > 0.f ? bf16_to_f32(gv[u][j]) : 0.f;
-        float xhat = (bf16_to_f32(xv[u][j]) - mu[j]) * is[j];
-        adb[j] += g;
-        ads[j] += g * xhat;
-        if (WRITE_DYM) dm[j] = f32_to_bf16(g);
+      for (int u = 0; u < U; u++) {
+        k[u] = (row + (h + u) * stride) * CG + cg;
+        xv[u] = x[k[u]];
+        yv[u] = y[k[u]];
+        gv[u] = dy[k[u]];
+        if (WITH_DY2) g2[u] = dy2[k[u]];
       }
-      if (WRITE_DYM) dym_out[k[u]] = dm;
+#pragma unroll
+      for (int u = 0; u < U; u++) {
+        ushort8 dm;
+#pragma unroll
+        for (int j = 0; j < 8; j++) {
+          float gin = WITH_DY2 ? bn_join_grad(gv[u][j], g2[u][j])
+                               : bf16_to_f32(gv[u][j]);
+          float g = bf16_to_f32(yv[u][j]) > 0.f ? gin : 0.f;
+          float xhat = (bf16_to_f32(xv[u][j]) - mu[j]) * is[j];
+          adb[j] += g;
+          ads[j] = bn_acc_dscale<true>(ads[j], g, xhat, j);
+          if (WRITE_DYM) dm[j] = f32_to_bf16(g);
+        }
+        if (WRITE_DYM) dym_out[k[u]] = dm;
+      }
     }
   }
   for (; row < M; row += stride) {
     const long long k = row * CG + cg;
     ushort8 xv = x[k], yv = y[k], gv = dy[k];
+    ushort8 g2;
+    if (WITH_DY2) g2 = dy2[k];
     ushort8 dm;
 #pragma unroll
     for (int j = 0; j < 8; j++) {
-      float g = bf16_to_f32(yv[j]) > 0.f ? bf16_to_f32(gv[j]) : 0.f;
+      float gin = WITH_DY2 ? bn_join_grad(gv[j], g2[j]) : bf16_to_f32(gv[j]);
+      float g = bf16_to_f32(yv[j]) > 0.f ? gin : 0.f;
       float xhat = (bf16_to_f32(xv[j]) - mu[j]) * is[j];
       adb[j] += g;
-      ads[j] += g * xhat;
+      ads[j] = bn_acc_dscale<false>(ads[j], g, xhat, j);
       if (WRITE_DYM) dm[j] = f32_to_bf16(g);
     }
     if (WRITE_DYM) dym_out[k] = dm;
@@ -796,10 +854,27 @@ std::vector<torch::Tensor> bn_relu_bwd(torch::Tensor x, torch::Tensor y,
                                        torch::Tensor dy, torch::Tensor weight,
                                        torch::Tensor bias, torch::Tensor mean,
                                        torch::Tensor invstd, bool need_dres,
-                                       bool relu) {
+                                       bool relu,
+                                       c10::optional<torch::Tensor> dy2) {
   TORCH_CHECK(relu || !need_dres,
               "bn_relu_bwd: residual path requires the ReLU variant");
   Geom g = geom_of(x);
+  TORCH_CHECK(dy.sizes() == x.sizes() && y.sizes() == x.sizes() &&
+                  dy.scalar_type() == at::kBFloat16,
+              "bn_relu_bwd: dy must be bf16 of x's shape");
+  // second upstream gradient (y forked to two consumers): folded into
+  // the residual stats kernel when it has dy's layout; anything else is
+  // summed here first and takes the existing path
+  bool fold_dy2 = false;
+  if (dy2.has_value() && dy2->defined()) {
+    TORCH_CHECK(dy2->sizes() == x.sizes(),
+                "bn_relu_bwd: dy2 must have x's shape");
+    fold_dy2 = need_dres && dy2->is_cuda() &&
+               dy2->scalar_type() == at::kBFloat16 &&
+               dy2->is_contiguous(at::MemoryFormat::ChannelsLast) &&
+               dy.is_contiguous(at::MemoryFormat::ChannelsLast);
+    if (!fold_dy2) dy = (dy + *dy2).to(at::kBFloat16);
+  }
   auto stream = at::cuda::getCurrentCUDAStream();
   auto f32 = x.options().dtype(at::kFloat);
   auto part = at::empty({(long long)2 * g.stat_blocks * g.C}, f32);
@@ -815,14 +890,21 @@ std::vector<torch::Tensor> bn_relu_bwd(torch::Tensor x, torch::Tensor y,
     // residual: the stats pass writes dym (= dres), the apply pass
     // reads it back instead of y AND dy (8 tensor passes -> 7)
     dres = at::empty_like(x);
-    hipLaunchKernelGGL(bn_bwd_stats_kernel<true>, dim3(g.stat_blocks),
-                       dim3(KS_BN_BLOCK), 0, stream.stream(),
-                       reinterpret_cast<const ushort8*>(x.data_ptr()),
-                       reinterpret_cast<const ushort8*>(y.data_ptr()),
-                       reinterpret_cast<const ushort8*>(dy.data_ptr()),
-                       reinterpret_cast<ushort8*>(dres.data_ptr()),
-                       mean.data_ptr<float>(), invstd.data_ptr<float>(),
-                       part.data_ptr<float>(), g.M, g.CG);
+    auto launch_rstats = [&](auto kern) {
+      hipLaunchKernelGGL(kern, dim3(g.stat_blocks), dim3(KS_BN_BLOCK), 0,
+                         stream.stream(),
+                         reinterpret_cast<const ushort8*>(x.data_ptr()),
+                         reinterpret_cast<const ushort8*>(y.data_ptr()),
+                         reinterpret_cast<const ushort8*>(dy.data_ptr()),
+                         fold_dy2 ? reinterpret_cast<const ushort8*>(
+                                        dy2->data_ptr())
+                                  : nullptr,
+                         reinterpret_cast<ushort8*>(dres.data_ptr()),
+                         mean.data_ptr<float>(), invstd.data_ptr<float>(),
+                         part.data_ptr<float>(), g.M, g.CG);
+    };
+    fold_dy2 ? launch_rstats(bn_bwd_stats_kernel<true, true>)
+             : launch_rstats(bn_bwd_stats_kernel<true, false>);
     hipLaunchKernelGGL(bn_reduce_partials_kernel,
                        dim3((g.C + 3) / 4), dim3(64, 4), 0, stream.stream(),
                        part.data_ptr<float>(), g.stat_blocks, g.C,

@@ -8,9 +8,12 @@
 //  - burn_kernel: wall-clock-bounded MFMA/VALU spin — a *calibrated GPU
 //    load generator* for the isolation tests and rocprof quota proofs
 //    (occupies all CUs for a requested number of microseconds).
-//  - multi-tensor SGD+momentum: one launch per dtype-bucket chunk set,
-//    grid-stride, float4/bf16x8-vectorized (guide G13: vectorize ANY
-//    memory-bound op; scalar bf16 ~2-2.5x slower).
+//  - sgd_mom_f32_kernel: SGD+momentum on one f32 tensor, grid-stride,
+//    float4-vectorized (guide G13: vectorize ANY memory-bound op). Kept
+//    as the bit-exact reference and for KUBESHARE_SGD_MULTI=0.
+//  - sgd_mom_multi_f32_kernel: the same update for up to 110 tensors per
+//    launch; pointers and block prefix sums ride in the kernel arguments
+//    (ResNet50's 161 tensors: 2 launches instead of 161).
 //  - bn_relu.hip / pool.hip: fused NHWC bf16 BN+ReLU(+add) and max-pool
 //    (bound below).
 #include <hip/hip_runtime.h>
@@ -61,6 +64,27 @@ struct Vec4<float> {
   using type = float4;
 };
 
+// The one place the update is spelled out, shared by the per-tensor and
+// the multi-tensor kernel. The FMAs are explicit: left to -ffp-contract
+// the backend fused `mu*v + g + wd*p` in the float4 loops but emitted a
+// packed multiply and two adds in the scalar loops, so an element's
+// last bit depended on which loop it fell into. This is the float4
+// loops' sequence, now used for every element.
+__device__ __forceinline__ void sgd_mom_update(float& p, float g, float& v,
+                                               float lr, float mu, float wd) {
+  v = fmaf(wd, p, fmaf(mu, v, g));
+  p = fmaf(-lr, v, p);
+}
+
+__device__ __forceinline__ void sgd_mom_update4(float4& p, const float4& g,
+                                                float4& v, float lr, float mu,
+                                                float wd) {
+  sgd_mom_update(p.x, g.x, v.x, lr, mu, wd);
+  sgd_mom_update(p.y, g.y, v.y, lr, mu, wd);
+  sgd_mom_update(p.z, g.z, v.z, lr, mu, wd);
+  sgd_mom_update(p.w, g.w, v.w, lr, mu, wd);
+}
+
 __global__ void sgd_mom_f32_kernel(float* __restrict__ p,
                                    const float* __restrict__ g,
                                    float* __restrict__ v, float lr, float mu,
@@ -73,22 +97,112 @@ __global__ void sgd_mom_f32_kernel(float* __restrict__ p,
   float4* v4 = reinterpret_cast<float4*>(v);
   for (long long k = i; k < n4; k += stride) {
     float4 pv = p4[k], gv = g4[k], vv = v4[k];
-    vv.x = mu * vv.x + gv.x + wd * pv.x;
-    vv.y = mu * vv.y + gv.y + wd * pv.y;
-    vv.z = mu * vv.z + gv.z + wd * pv.z;
-    vv.w = mu * vv.w + gv.w + wd * pv.w;
-    pv.x -= lr * vv.x;
-    pv.y -= lr * vv.y;
-    pv.z -= lr * vv.z;
-    pv.w -= lr * vv.w;
+    sgd_mom_update4(pv, gv, vv, lr, mu, wd);
     v4[k] = vv;
     p4[k] = pv;
   }
   // tail
   for (long long k = n4 * 4 + i; k < n; k += stride) {
-    float vv = mu * v[k] + g[k] + wd * p[k];
+    float pv = p[k], vv = v[k];
+    sgd_mom_update(pv, g[k], vv, lr, mu, wd);
     v[k] = vv;
-    p[k] -= lr * vv;
+    p[k] = pv;
+  }
+}
+
+// ------------------------------------------------ multi-tensor variant
+// One launch updates up to KS_SGD_MAX_TENSORS (p, g, v) triples. The
+// pointers, element counts and a prefix sum of per-tensor block counts
+// travel BY VALUE in the kernel arguments (4096-byte limit): there is no
+// device-side pointer table that could go stale between steps. A block
+// binary-searches the prefix sum for its tensor and owns one
+// KS_SGD_CHUNK-element chunk of it.
+#define KS_SGD_THREADS 256
+#define KS_SGD_VPT 4  // float4 per thread: 4 independent 16-B loads x 3
+#define KS_SGD_CHUNK (KS_SGD_THREADS * KS_SGD_VPT * 4)
+#define KS_SGD_MAX_TENSORS 110
+
+struct SgdMultiArgs {
+  float* p[KS_SGD_MAX_TENSORS];
+  const float* g[KS_SGD_MAX_TENSORS];
+  float* v[KS_SGD_MAX_TENSORS];
+  long long n[KS_SGD_MAX_TENSORS];
+  // blk[t] = first block of tensor t; blk[count] = grid size
+  int blk[KS_SGD_MAX_TENSORS + 1];
+  int count;
+  float lr, mu, wd;
+};
+static_assert(sizeof(SgdMultiArgs) <= 4096,
+              "SgdMultiArgs must fit the 4 KiB kernel-argument segment");
+
+__global__ void __launch_bounds__(KS_SGD_THREADS)
+sgd_mom_multi_f32_kernel(const SgdMultiArgs a) {
+  const int b = blockIdx.x;
+  // largest t with blk[t] <= b (blk is non-decreasing, blk[0] == 0,
+  // b < blk[count]; tensors own >= 1 block, so the answer is unique)
+  int lo = 0, hi = a.count - 1;
+  while (lo < hi) {
+    int mid = (lo + hi + 1) >> 1;
+    if (a.blk[mid] <= b) lo = mid; else hi = mid - 1;
+  }
+  float* __restrict__ p = a.p[lo];
+  const float* __restrict__ g = a.g[lo];
+  float* __restrict__ v = a.v[lo];
+  const long long n = a.n[lo];
+  const float lr = a.lr, mu = a.mu, wd = a.wd;
+  const long long base = (long long)(b - a.blk[lo]) * KS_SGD_CHUNK;
+  long long rem = n - base;  // > 0 by construction of blk
+  const int len = rem < KS_SGD_CHUNK ? (int)rem : KS_SGD_CHUNK;
+  p += base;
+  g += base;
+  v += base;
+  const int tid = threadIdx.x;
+  // base is a multiple of 4 elements, so the chunk start is 16-byte
+  // aligned exactly when the tensor start is; misaligned views
+  // (narrow() at an odd offset) take the scalar path
+  const bool vec = (((uintptr_t)p | (uintptr_t)g | (uintptr_t)v) & 15) == 0;
+  if (vec) {
+    const int len4 = len >> 2;
+    const float4* g4 = reinterpret_cast<const float4*>(g);
+    float4* p4 = reinterpret_cast<float4*>(p);
+    float4* v4 = reinterpret_cast<float4*>(v);
+    if (len == KS_SGD_CHUNK) {
+      float4 pv[KS_SGD_VPT], gv[KS_SGD_VPT], vv[KS_SGD_VPT];
+#pragma unroll
+      for (int u = 0; u < KS_SGD_VPT; u++) {
+        const int k = tid + u * KS_SGD_THREADS;
+        pv[u] = p4[k];
+        gv[u] = g4[k];
+        vv[u] = v4[k];
+      }
+#pragma unroll
+      for (int u = 0; u < KS_SGD_VPT; u++) {
+        const int k = tid + u * KS_SGD_THREADS;
+        sgd_mom_update4(pv[u], gv[u], vv[u], lr, mu, wd);
+        v4[k] = vv[u];
+        p4[k] = pv[u];
+      }
+      return;
+    }
+    for (int k = tid; k < len4; k += KS_SGD_THREADS) {
+      float4 pv = p4[k], gv = g4[k], vv = v4[k];
+      sgd_mom_update4(pv, gv, vv, lr, mu, wd);
+      v4[k] = vv;
+      p4[k] = pv;
+    }
+    for (int k = len4 * 4 + tid; k < len; k += KS_SGD_THREADS) {
+      float pv = p[k], vv = v[k];
+      sgd_mom_update(pv, g[k], vv, lr, mu, wd);
+      v[k] = vv;
+      p[k] = pv;
+    }
+    return;
+  }
+  for (int k = tid; k < len; k += KS_SGD_THREADS) {
+    float pv = p[k], vv = v[k];
+    sgd_mom_update(pv, g[k], vv, lr, mu, wd);
+    v[k] = vv;
+    p[k] = pv;
   }
 }
 
@@ -120,6 +234,81 @@ void sgd_momentum_(std::vector<torch::Tensor> params,
   }
 }
 
+// All triples in ceil(count / KS_SGD_MAX_TENSORS) launches (ResNet50: 161
+// tensors -> 2). grads[t] may be None: that tensor is skipped. Returns
+// the number of kernels launched.
+int64_t sgd_momentum_multi_(std::vector<torch::Tensor> params,
+                            std::vector<c10::optional<torch::Tensor>> grads,
+                            std::vector<torch::Tensor> momenta, double lr,
+                            double mu, double wd) {
+  TORCH_CHECK(params.size() == grads.size() &&
+                  params.size() == momenta.size(),
+              "sgd_momentum_multi_: params, grads and momenta differ in "
+              "length");
+  auto stream = at::cuda::getCurrentCUDAStream();
+  const long long max_blocks = 1LL << 30;
+  SgdMultiArgs a = {};
+  a.lr = (float)lr;
+  a.mu = (float)mu;
+  a.wd = (float)wd;
+  a.count = 0;
+  a.blk[0] = 0;
+  int64_t launches = 0;
+  // re-strided gradient copies live until every launch is enqueued
+  std::vector<torch::Tensor> keep;
+  auto flush = [&]() {
+    if (a.count == 0) return;
+    hipLaunchKernelGGL(sgd_mom_multi_f32_kernel, dim3(a.blk[a.count]),
+                       dim3(KS_SGD_THREADS), 0, stream.stream(), a);
+    launches++;
+    a.count = 0;
+  };
+  for (size_t t = 0; t < params.size(); t++) {
+    if (!grads[t].has_value() || !grads[t]->defined()) continue;
+    auto& p = params[t];
+    auto& v = momenta[t];
+    torch::Tensor g = *grads[t];
+    TORCH_CHECK(g.sizes() == p.sizes() && g.is_cuda() &&
+                    g.scalar_type() == at::kFloat,
+                "sgd_momentum_multi_: f32 CUDA gradient of the "
+                "parameter's shape expected");
+    if (g.strides() != p.strides()) {
+      // rare: e.g. a contiguous gradient for a channels-last weight
+      g = at::empty_like(p).copy_(g);
+      keep.push_back(g);
+    }
+    TORCH_CHECK(p.is_cuda() && p.scalar_type() == at::kFloat &&
+                    p.is_non_overlapping_and_dense() &&
+                    g.sizes() == p.sizes() && g.strides() == p.strides() &&
+                    v.strides() == p.strides() &&
+                    g.scalar_type() == at::kFloat &&
+                    v.scalar_type() == at::kFloat,
+                "sgd_momentum_: f32 dense tensors with matching strides "
+                "(any memory format: the update is elementwise over the "
+                "flat storage)");
+    TORCH_CHECK(v.is_cuda() && v.sizes() == p.sizes() &&
+                    p.get_device() == stream.device_index() &&
+                    g.get_device() == p.get_device() &&
+                    v.get_device() == p.get_device(),
+                "sgd_momentum_multi_: parameter, gradient and momentum "
+                "must live on the current device and share a shape");
+    const long long n = p.numel();
+    if (n == 0) continue;
+    const long long nb = (n + KS_SGD_CHUNK - 1) / KS_SGD_CHUNK;
+    TORCH_CHECK(nb <= max_blocks, "sgd_momentum_multi_: tensor too large");
+    if (a.count == KS_SGD_MAX_TENSORS || a.blk[a.count] + nb > max_blocks)
+      flush();
+    a.p[a.count] = p.data_ptr<float>();
+    a.g[a.count] = g.data_ptr<float>();
+    a.v[a.count] = v.data_ptr<float>();
+    a.n[a.count] = n;
+    a.blk[a.count + 1] = a.blk[a.count] + (int)nb;
+    a.count++;
+  }
+  flush();
+  return launches;
+}
+
 // fused NHWC bf16 BatchNorm+ReLU (bn_relu.hip)
 std::vector<torch::Tensor> bn_relu_fwd_train(
     torch::Tensor x, torch::Tensor weight, torch::Tensor bias,
@@ -133,7 +322,8 @@ std::vector<torch::Tensor> bn_relu_bwd(torch::Tensor x, torch::Tensor y,
                                        torch::Tensor dy, torch::Tensor weight,
                                        torch::Tensor bias, torch::Tensor mean,
                                        torch::Tensor invstd, bool need_dres,
-                                       bool relu);
+                                       bool relu,
+                                       c10::optional<torch::Tensor> dy2);
 
 // fused NHWC bf16 max-pool, one-byte argmax + gather backward (pool.hip)
 std::vector<torch::Tensor> max_pool_nhwc_fwd(torch::Tensor x, int64_t k,
@@ -148,9 +338,16 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("ms"), py::arg("blocks") = 1024, py::arg("threads") = 256);
   m.def("sgd_momentum_", &sgd_momentum_,
         "fused SGD+momentum update (in-place)");
+  m.def("sgd_momentum_multi_", &sgd_momentum_multi_,
+        "fused SGD+momentum update of all tensors in as few launches as "
+        "the kernel-argument limit allows; a None gradient skips its "
+        "tensor; returns the number of launches");
   m.def("bn_relu_fwd_train", &bn_relu_fwd_train);
   m.def("bn_relu_fwd_eval", &bn_relu_fwd_eval);
-  m.def("bn_relu_bwd", &bn_relu_bwd);
+  m.def("bn_relu_bwd", &bn_relu_bwd, py::arg("x"), py::arg("y"),
+        py::arg("dy"), py::arg("weight"), py::arg("bias"), py::arg("mean"),
+        py::arg("invstd"), py::arg("need_dres"), py::arg("relu"),
+        py::arg("dy2") = py::none());
   m.def("max_pool_nhwc_fwd", &max_pool_nhwc_fwd);
   m.def("max_pool_nhwc_bwd", &max_pool_nhwc_bwd);
 }
