@@ -12,6 +12,7 @@ from __future__ import annotations
 import torch
 import torch.nn as nn
 
+from .conv import LowpConv2d
 from .pool import FusedMaxPool2d
 
 
@@ -22,18 +23,18 @@ class Bottleneck(nn.Module):
     def __init__(self, in_ch: int, width: int, stride: int = 1):
         super().__init__()
         out_ch = width * self.expansion
-        self.conv1 = nn.Conv2d(in_ch, width, 1, bias=False)
+        self.conv1 = LowpConv2d(in_ch, width, 1, bias=False)
         self.bn1 = nn.BatchNorm2d(width)
-        self.conv2 = nn.Conv2d(width, width, 3, stride=stride, padding=1,
-                               bias=False)
+        self.conv2 = LowpConv2d(width, width, 3, stride=stride, padding=1,
+                                bias=False)
         self.bn2 = nn.BatchNorm2d(width)
-        self.conv3 = nn.Conv2d(width, out_ch, 1, bias=False)
+        self.conv3 = LowpConv2d(width, out_ch, 1, bias=False)
         self.bn3 = nn.BatchNorm2d(out_ch)
         self.relu = nn.ReLU(inplace=True)
         self.down = None
         if stride != 1 or in_ch != out_ch:
             self.down = nn.Sequential(
-                nn.Conv2d(in_ch, out_ch, 1, stride=stride, bias=False),
+                LowpConv2d(in_ch, out_ch, 1, stride=stride, bias=False),
                 nn.BatchNorm2d(out_ch),
             )
 
@@ -68,16 +69,16 @@ class BasicBlock(nn.Module):
 
     def __init__(self, in_ch: int, width: int, stride: int = 1):
         super().__init__()
-        self.conv1 = nn.Conv2d(in_ch, width, 3, stride=stride, padding=1,
-                               bias=False)
+        self.conv1 = LowpConv2d(in_ch, width, 3, stride=stride, padding=1,
+                                bias=False)
         self.bn1 = nn.BatchNorm2d(width)
-        self.conv2 = nn.Conv2d(width, width, 3, padding=1, bias=False)
+        self.conv2 = LowpConv2d(width, width, 3, padding=1, bias=False)
         self.bn2 = nn.BatchNorm2d(width)
         self.relu = nn.ReLU(inplace=True)
         self.down = None
         if stride != 1 or in_ch != width:
             self.down = nn.Sequential(
-                nn.Conv2d(in_ch, width, 1, stride=stride, bias=False),
+                LowpConv2d(in_ch, width, 1, stride=stride, bias=False),
                 nn.BatchNorm2d(width),
             )
 
@@ -104,7 +105,7 @@ class ResNet(nn.Module):
     def __init__(self, block, layers, num_classes: int = 1000):
         super().__init__()
         self.in_ch = 64
-        self.conv1 = nn.Conv2d(3, 64, 7, stride=2, padding=3, bias=False)
+        self.conv1 = LowpConv2d(3, 64, 7, stride=2, padding=3, bias=False)
         self.bn1 = nn.BatchNorm2d(64)
         self.relu = nn.ReLU(inplace=True)
         self.maxpool = FusedMaxPool2d(3, stride=2, padding=1)
@@ -121,6 +122,10 @@ class ResNet(nn.Module):
             elif isinstance(m, nn.BatchNorm2d):
                 nn.init.ones_(m.weight)
                 nn.init.zeros_(m.bias)
+        # every conv of the model, for ops.stage_lowp_weights (a plain
+        # list: not a registered submodule container)
+        self._lowp_convs = [m for m in self.modules()
+                            if isinstance(m, LowpConv2d)]
 
     def _make_layer(self, block, width, n, stride=1):
         layers = [block(self.in_ch, width, stride)]
@@ -129,6 +134,19 @@ class ResNet(nn.Module):
         return nn.Sequential(*layers)
 
     def forward(self, x):
+        if not self.fused_ops:
+            return self._forward(x)
+        from .. import ops
+        # one launch casts every conv weight for this forward (bf16
+        # autocast only; otherwise nothing is staged and the convs use
+        # self.weight); the staged copies are dropped on the way out
+        staged = ops.stage_lowp_weights(self._lowp_convs)
+        try:
+            return self._forward(x)
+        finally:
+            ops.clear_lowp_weights(staged)
+
+    def _forward(self, x):
         if self.fused_ops:
             from .. import ops
             x = self.maxpool(ops.bn_relu(self.conv1(x), self.bn1))

@@ -13,7 +13,8 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 _BUILD_DIR = os.path.join(_HERE, "_build")
 _SRCS = [os.path.join(_HERE, "hip", "ks_ops.hip"),
          os.path.join(_HERE, "hip", "bn_relu.hip"),
-         os.path.join(_HERE, "hip", "pool.hip")]
+         os.path.join(_HERE, "hip", "pool.hip"),
+         os.path.join(_HERE, "hip", "cast.hip")]
 
 _ext = None
 
@@ -190,7 +191,12 @@ def _bn_relu_autograd():
         8-pass backward (incl. separate ReLU and residual-add kernels)
         with 3 forward passes and 5 (non-residual, mask recomputed
         from x) / 7 (residual, dym reuse) backward passes — see
-        profiles/README.md for the motivation.
+        profiles/README.md for the motivation. Each direction is three
+        launches: stats, one coalesced reduce of the block partials
+        (which in forward also finalizes mean/invstd, the running stats
+        and the folded scale/bias), apply. KUBESHARE_BN_REDUCE=legacy
+        (see bn_reduce_legacy) runs the earlier reduce and finalize
+        kernels instead; both compute the same bits.
 
         fork=True returns the pair (y, y2) with y2 = y.view_as(y): the
         same memory under two autograd edges, one per consumer of a
@@ -214,10 +220,11 @@ def _bn_relu_autograd():
             ctx.with_res = res is not None
             ctx.relu = relu
             ctx.wdtype = weight.dtype
+            ctx.legacy_reduce = bn_reduce_legacy()
             if training:
                 y, mean, invstd = ext.bn_relu_fwd_train(
                     x, w32, b32, running_mean, running_var, momentum, eps,
-                    res, relu)
+                    res, relu, ctx.legacy_reduce)
                 ctx.save_for_backward(x, y, w32, b32, mean, invstd)
             else:
                 y = ext.bn_relu_fwd_eval(x, w32, b32, running_mean.float(),
@@ -235,7 +242,8 @@ def _bn_relu_autograd():
             if dy is None:  # no gradient reached either output
                 return (None,) * 11
             out = ext.bn_relu_bwd(x, y, dy, w32, b32, mean, invstd,
-                                  ctx.with_res, ctx.relu, dy2)
+                                  ctx.with_res, ctx.relu, dy2,
+                                  ctx.legacy_reduce)
             dx, dscale, dbias = out[0], out[1], out[2]
             dres = out[3] if ctx.with_res else None
             return (dx, dres, dscale.to(ctx.wdtype), dbias.to(ctx.wdtype),
@@ -253,6 +261,15 @@ def bn_fork_enabled() -> bool:
     sums the two gradients with its own add kernel); A/B runs, operator
     escape hatch."""
     return os.environ.get("KUBESHARE_BN_FORK", "1") != "0"
+
+
+def bn_reduce_legacy() -> bool:
+    """KUBESHARE_BN_REDUCE=legacy reduces the BN block partials with the
+    earlier one-wave-per-channel kernel and, in forward, a separate
+    finalize launch, instead of the coalesced reduce(+finalize) kernel.
+    Same results bit for bit; A/B runs and the oracle of
+    tests/test_bn_reduce_gpu.py."""
+    return os.environ.get("KUBESHARE_BN_REDUCE", "") == "legacy"
 
 
 def bn_relu(x, bn, res=None, relu=True, fork=False):
@@ -287,6 +304,89 @@ def bn_relu(x, bn, res=None, relu=True, fork=False):
     return fn.apply(x, res, bn.weight, bn.bias, bn.running_mean,
                     bn.running_var, bn.training, bn.momentum, bn.eps, relu,
                     fork)
+
+
+# ------------------------------------------- multi-tensor weight casts
+_CastWeightsFn = None
+
+
+def _cast_weights_autograd():
+    """Lazily build the autograd.Function (torch import deferred)."""
+    global _CastWeightsFn
+    if _CastWeightsFn is not None:
+        return _CastWeightsFn
+    import torch
+
+    class CastWeightsFn(torch.autograd.Function):
+        """(w0, w1, ...) f32 -> (bf16 copies) in one multi-tensor launch
+        of hip/cast.hip per 128 tensors, strides preserved; the backward
+        casts the incoming bf16 gradients back to f32 the same way. A
+        gradient that is already f32, or None, passes through untouched.
+        Values are exactly those of w.to(torch.bfloat16) and g.float():
+        this replaces autocast's per-weight cast launches and their
+        ToCopyBackward0 nodes, nothing else."""
+
+        @staticmethod
+        def forward(ctx, *weights):
+            ctx.set_materialize_grads(False)
+            return tuple(_load().cast_f32_to_bf16_multi(list(weights)))
+
+        @staticmethod
+        def backward(ctx, *grads):
+            out = list(grads)
+            idx = [i for i, g in enumerate(grads)
+                   if g is not None and g.dtype == torch.bfloat16]
+            if idx:
+                cast = _load().cast_bf16_to_f32_multi(
+                    [grads[i] for i in idx])
+                for i, g in zip(idx, cast):
+                    out[i] = g
+            return tuple(out)
+
+    _CastWeightsFn = CastWeightsFn
+    return CastWeightsFn
+
+
+def cast_weights_bf16(weights):
+    """bf16 copies of a sequence of f32 CUDA tensors through
+    CastWeightsFn (differentiable; works under no_grad and inside a
+    hipGraph capture: addresses ride in the kernel arguments)."""
+    fn = _CastWeightsFn or _cast_weights_autograd()
+    return fn.apply(*weights)
+
+
+def lowp_weights_enabled() -> bool:
+    """KUBESHARE_LOWP_WEIGHTS=0 leaves every conv weight to autocast's
+    own per-tensor cast (A/B runs, operator escape hatch)."""
+    return os.environ.get("KUBESHARE_LOWP_WEIGHTS", "1") != "0"
+
+
+def stage_lowp_weights(convs):
+    """Give every models.conv.LowpConv2d in `convs` a bf16 copy of its
+    weight for the forward in progress, all cast by one launch. Happens
+    only under CUDA autocast with dtype bf16, for f32 CUDA weights, and
+    unless KUBESHARE_LOWP_WEIGHTS=0; otherwise nothing is staged and the
+    convs use self.weight as ever. Returns the modules staged, for
+    clear_lowp_weights."""
+    import torch
+
+    if not convs or not lowp_weights_enabled():
+        return []
+    if not torch.is_autocast_enabled("cuda") or \
+            torch.get_autocast_dtype("cuda") != torch.bfloat16:
+        return []
+    weights = [m.weight for m in convs]
+    if not all(w.is_cuda and w.dtype == torch.float32 for w in weights):
+        return []
+    for m, w in zip(convs, cast_weights_bf16(weights)):
+        m._lowp_weight = w
+    return convs
+
+
+def clear_lowp_weights(convs):
+    """Drop the staged copies (the autograd graph keeps what it needs)."""
+    for m in convs:
+        m._lowp_weight = None
 
 
 # ------------------------------------------------------ fused max-pool
@@ -396,7 +496,8 @@ def max_pool_nhwc(x, kernel_size, stride=None, padding=0):
 def fuse_model(model):
     """Enable the fused BN+ReLU(+add) and max-pool paths on
     kubeshare_amd models (blocks and pool modules check their
-    `fused_ops` flag); verifies the extension
+    `fused_ops` flag; a flagged ResNet also stages its conv weights,
+    see stage_lowp_weights); verifies the extension
     is importable first (fail-loud on GPU boxes)."""
     _load()
     for m in model.modules():

@@ -18,10 +18,24 @@
 //  - UNROLL independent row-chunks per loop iteration so each lane
 //    keeps >=4 16-B loads in flight (1 load/lane measured ~2.3 TB/s,
 //    HBM-latency-bound at 32 waves/CU).
-//  - block partials + a tree-reduce in the finalize kernel instead of
+//  - block partials + a tree-reduce in a second kernel instead of
 //    per-channel global atomics (2*C atomics x 2048 blocks measured as
 //    ~0.4 ms of fixed cost per BN call).
 //  - all stats/parameter math in f32; tensors read/written as bf16x8.
+//
+// Launch sequence (three launches each):
+//   forward   bn_stats -> bn_reduce_tile<FINALIZE> -> bn_apply_relu
+//   backward  bn_bwd_stats[_noy] -> bn_reduce_tile -> bn_bwd_apply_*
+// The stats kernels leave part[b*C + c] (second half at + nblocks*C);
+// bn_reduce_tile_kernel sums it over b with its lanes along c (coalesced)
+// and, in forward, goes straight on to the per-channel finalize math.
+// Reduce contract, per channel and half: 64 accumulators a[L] take the
+// blocks b = L, L+64, ... in ascending order, then a[i] += a[i+off] for
+// off = 32 .. 1; see bn_reduce_tile_kernel. legacy_reduce=true (Python:
+// KUBESHARE_BN_REDUCE=legacy) runs the earlier bn_reduce_partials_kernel
+// (+ bn_finalize_kernel in forward) instead: same sums bit for bit, one
+// wave per channel reading 4 bytes of each of 64 rows per instruction.
+// It is the oracle of tests/test_bn_reduce_gpu.py and the A/B baseline.
 #include <hip/hip_runtime.h>
 #include <torch/extension.h>
 #include <ATen/cuda/CUDAContext.h>
@@ -132,8 +146,9 @@ __global__ void bn_stats_kernel(const ushort8* __restrict__ x,
   }
 }
 
-// ------------------------------------------------- partial reduction
+// ---------------------------------------- partial reduction (legacy)
 // part[b*C + c] (+ the sq/dscale half at offset nblocks*C) -> out[c].
+// Kept for legacy_reduce=true; bn_reduce_tile_kernel replaces it.
 // One 64-lane wave per 4 channels: lanes stride over blocks (all loads
 // independent -> one latency, not nblocks of them), then shfl-reduce.
 __global__ void bn_reduce_partials_kernel(const float* __restrict__ part,
@@ -160,8 +175,146 @@ __global__ void bn_reduce_partials_kernel(const float* __restrict__ part,
 }
 
 // ------------------------------------------------------- fwd finalize
-// Reduce the block partials, then mean/invstd, running-stat update
-// (PyTorch semantics), and folded scale' = w*invstd, bias' = b - mean*s.
+// One channel's mean/invstd, running-stat update (PyTorch semantics) and
+// folded scale' = w*invstd, bias' = b - mean*s, from its two sums.
+// Pinned: left to -ffp-contract, which of these expressions become FMAs
+// depends on the kernel they are inlined into. The sequence written out
+// here is the one the stand-alone bn_finalize_kernel always compiled to
+// (read from its ISA): var and bias' use an FMA, the running-stat
+// updates two rounded products and an add.
+struct BnFinalizeArgs {
+  const float* __restrict__ weight;
+  const float* __restrict__ bias;
+  float* __restrict__ running_mean;  // may be null (with running_var)
+  float* __restrict__ running_var;
+  float* __restrict__ save_mean;
+  float* __restrict__ save_invstd;
+  float* __restrict__ scale_out;
+  float* __restrict__ bias_out;
+  long long M;
+  float momentum, eps;
+};
+
+__device__ __forceinline__ void bn_finalize_channel(const BnFinalizeArgs& f,
+                                                    int c, float sum,
+                                                    float sumsq) {
+#pragma clang fp contract(off)
+  const long long M = f.M;
+  float mean = sum / (float)M;
+  float var = fmaf(-mean, mean, sumsq / (float)M);
+  var = var < 0.f ? 0.f : var;
+  float invstd = rsqrtf(var + f.eps);
+  f.save_mean[c] = mean;
+  f.save_invstd[c] = invstd;
+  if (f.running_mean) {
+    float unbiased = M > 1 ? var * (float)M / (float)(M - 1) : var;
+    const float keep = 1.f - f.momentum;
+    float rm = keep * f.running_mean[c];
+    float rv = keep * f.running_var[c];
+    float nm = f.momentum * mean;
+    float nv = f.momentum * unbiased;
+    f.running_mean[c] = rm + nm;
+    f.running_var[c] = rv + nv;
+  }
+  float s = f.weight[c] * invstd;
+  f.scale_out[c] = s;
+  f.bias_out[c] = fmaf(-mean, s, f.bias[c]);
+}
+
+// ------------------------------------- coalesced reduce (+ fwd finalize)
+// Same sums as bn_reduce_partials_kernel, bit for bit, with the lanes
+// running along CHANNELS: a block owns TILE consecutive channels and 64
+// accumulators per channel and half, so a wave instruction reads
+// 64/TILE rows of TILE*4 contiguous bytes instead of 64 rows of 4.
+//
+// Contract (per channel, separately for the two halves of `part`):
+//   a[L] = 0.f; a[L] += part[b][c] for b = L, L+64, L+128, ... ascending
+//   for off in 32,16,8,4,2,1: a[i] += a[i+off] for i < off
+//   result = a[0]
+// which is the legacy kernel's __shfl_down tree as lane 0 sees it.
+//
+// Mapping: thread = (wave w, k, cc) with lane = k*TILE + cc and
+// L = w + NW*k (NW = TILE waves per block). The tree steps off >= NW
+// pair accumulators of one wave (lane distance off/NW*TILE: shuffles);
+// the NW survivors per channel go through LDS to a second set of
+// shuffles in which lane = L*QC + q carries channel wave*QC + q.
+// FINALIZE: the lanes that end up with a channel's two sums go straight
+// on to bn_finalize_channel (no `sums` buffer, no finalize launch).
+// Swept in the ResNet50 bs256 step (average us per call, forward /
+// backward): TILE 16 x 8 loads 7.5 / 6.8, TILE 16 x 16 loads 7.8 / 6.9,
+// TILE 8 x 8 loads 7.9 / 7.0 — flat; what is left is mostly the cost
+// of a dependent launch (bn_finalize_kernel alone took 4.8).
+#define KS_BN_RTILE 16
+#define KS_BN_RLOADS 8  // independent loads in flight per half and thread
+
+template <int TILE, bool FINALIZE>
+__global__ void __launch_bounds__(64 * TILE)
+bn_reduce_tile_kernel(const float* __restrict__ part, int nblocks, int C,
+                      float* __restrict__ out0, float* __restrict__ out1,
+                      const BnFinalizeArgs fin) {
+  constexpr int NW = TILE;       // waves per block
+  constexpr int QC = 64 / NW;    // channels per wave in the second stage
+  static_assert(TILE == 8 || TILE == 16, "64 % TILE, 64 * TILE <= 1024");
+  __shared__ float s_a[2][NW][TILE];
+  const int tid = threadIdx.x;
+  const int lane = tid & 63;
+  const int w = tid >> 6;
+  const int cc = lane % TILE;
+  const int L = w + NW * (lane / TILE);
+  const int c = blockIdx.x * TILE + cc;
+  const bool valid = c < C;  // C % 8 == 0: the last tile may be partial
+  const float* p0 = part + c;
+  const float* p1 = part + (long long)nblocks * C + c;
+  float a0 = 0.f, a1 = 0.f;
+  for (int b0 = L; b0 < nblocks; b0 += 64 * KS_BN_RLOADS) {
+    float v0[KS_BN_RLOADS], v1[KS_BN_RLOADS];
+#pragma unroll
+    for (int u = 0; u < KS_BN_RLOADS; u++) {
+      const int b = b0 + 64 * u;
+      const bool ok = valid && b < nblocks;
+      v0[u] = ok ? p0[(long long)b * C] : 0.f;
+      v1[u] = ok ? p1[(long long)b * C] : 0.f;
+    }
+#pragma unroll
+    for (int u = 0; u < KS_BN_RLOADS; u++)
+      if (b0 + 64 * u < nblocks) {
+        a0 += v0[u];
+        a1 += v1[u];
+      }
+  }
+  // tree steps 32 .. NW inside the wave
+#pragma unroll
+  for (int off = 32; off >= NW; off >>= 1) {
+    a0 += __shfl_down(a0, off / NW * TILE, 64);
+    a1 += __shfl_down(a1, off / NW * TILE, 64);
+  }
+  if (lane < TILE) {  // L == w: a[0 .. NW-1] of channel cc
+    s_a[0][w][cc] = a0;
+    s_a[1][w][cc] = a1;
+  }
+  __syncthreads();
+  if (tid >= 64 * (TILE / QC)) return;  // whole waves leave
+  const int l2 = lane / QC;             // 0 .. NW-1
+  const int cc2 = w * QC + lane % QC;
+  a0 = s_a[0][l2][cc2];
+  a1 = s_a[1][l2][cc2];
+#pragma unroll
+  for (int off = NW / 2; off > 0; off >>= 1) {
+    a0 += __shfl_down(a0, off * QC, 64);
+    a1 += __shfl_down(a1, off * QC, 64);
+  }
+  const int c2 = blockIdx.x * TILE + cc2;
+  if (l2 != 0 || c2 >= C) return;
+  if (FINALIZE) {
+    bn_finalize_channel(fin, c2, a0, a1);
+  } else {
+    out0[c2] = a0;
+    out1[c2] = a1;
+  }
+}
+
+// Legacy finalize launch (KUBESHARE_BN_REDUCE=legacy), after
+// bn_reduce_partials_kernel.
 __global__ void bn_finalize_kernel(const float* __restrict__ sum,
                                    const float* __restrict__ sumsq,
                                    const float* __restrict__ weight,
@@ -176,20 +329,10 @@ __global__ void bn_finalize_kernel(const float* __restrict__ sum,
                                    float eps) {
   int c = blockIdx.x * blockDim.x + threadIdx.x;
   if (c >= C) return;
-  float mean = sum[c] / (float)M;
-  float var = sumsq[c] / (float)M - mean * mean;
-  var = var < 0.f ? 0.f : var;
-  float invstd = rsqrtf(var + eps);
-  save_mean[c] = mean;
-  save_invstd[c] = invstd;
-  if (running_mean) {
-    float unbiased = M > 1 ? var * (float)M / (float)(M - 1) : var;
-    running_mean[c] = (1.f - momentum) * running_mean[c] + momentum * mean;
-    running_var[c] = (1.f - momentum) * running_var[c] + momentum * unbiased;
-  }
-  float s = weight[c] * invstd;
-  scale_out[c] = s;
-  bias_out[c] = bias[c] - mean * s;
+  const BnFinalizeArgs f = {weight, bias, running_mean, running_var,
+                            save_mean, save_invstd, scale_out, bias_out,
+                            M, momentum, eps};
+  bn_finalize_channel(f, c, sum[c], sumsq[c]);
 }
 
 // --------------------------------------------------------- fwd apply
@@ -761,7 +904,8 @@ Geom geom_of(const torch::Tensor& x) {
 std::vector<torch::Tensor> bn_relu_fwd_train(
     torch::Tensor x, torch::Tensor weight, torch::Tensor bias,
     torch::Tensor running_mean, torch::Tensor running_var, double momentum,
-    double eps, c10::optional<torch::Tensor> res, bool relu) {
+    double eps, c10::optional<torch::Tensor> res, bool relu,
+    bool legacy_reduce) {
   Geom g = geom_of(x);
   auto stream = at::cuda::getCurrentCUDAStream();
   auto f32 = x.options().dtype(at::kFloat);
@@ -771,29 +915,42 @@ std::vector<torch::Tensor> bn_relu_fwd_train(
   auto save_invstd = at::empty({g.C}, f32);
   auto scale = at::empty({g.C}, f32);
   auto biasf = at::empty({g.C}, f32);
-  auto sums = at::empty({2 * g.C}, f32);
+  float* rmean_p =
+      running_mean.defined() ? running_mean.data_ptr<float>() : nullptr;
+  float* rvar_p =
+      running_var.defined() ? running_var.data_ptr<float>() : nullptr;
 
   hipLaunchKernelGGL(bn_stats_kernel, dim3(g.stat_blocks),
                      dim3(KS_BN_BLOCK), 0, stream.stream(),
                      reinterpret_cast<const ushort8*>(x.data_ptr()),
                      part.data_ptr<float>(), g.M, g.CG);
-  hipLaunchKernelGGL(bn_reduce_partials_kernel,
-                     dim3((g.C + 3) / 4), dim3(64, 4), 0, stream.stream(),
-                     part.data_ptr<float>(), g.stat_blocks, g.C,
-                     sums.data_ptr<float>(), sums.data_ptr<float>() + g.C);
-  int fb = (g.C + 255) / 256;
-  hipLaunchKernelGGL(bn_finalize_kernel, dim3(fb), dim3(256), 0,
-                     stream.stream(), sums.data_ptr<float>(),
-                     sums.data_ptr<float>() + g.C,
-                     weight.data_ptr<float>(), bias.data_ptr<float>(),
-                     running_mean.defined()
-                         ? running_mean.data_ptr<float>() : nullptr,
-                     running_var.defined()
-                         ? running_var.data_ptr<float>() : nullptr,
-                     save_mean.data_ptr<float>(),
-                     save_invstd.data_ptr<float>(), scale.data_ptr<float>(),
-                     biasf.data_ptr<float>(), g.M, g.C, (float)momentum,
-                     (float)eps);
+  if (legacy_reduce) {
+    auto sums = at::empty({2 * g.C}, f32);
+    hipLaunchKernelGGL(bn_reduce_partials_kernel,
+                       dim3((g.C + 3) / 4), dim3(64, 4), 0, stream.stream(),
+                       part.data_ptr<float>(), g.stat_blocks, g.C,
+                       sums.data_ptr<float>(), sums.data_ptr<float>() + g.C);
+    int fb = (g.C + 255) / 256;
+    hipLaunchKernelGGL(bn_finalize_kernel, dim3(fb), dim3(256), 0,
+                       stream.stream(), sums.data_ptr<float>(),
+                       sums.data_ptr<float>() + g.C,
+                       weight.data_ptr<float>(), bias.data_ptr<float>(),
+                       rmean_p, rvar_p, save_mean.data_ptr<float>(),
+                       save_invstd.data_ptr<float>(),
+                       scale.data_ptr<float>(), biasf.data_ptr<float>(), g.M,
+                       g.C, (float)momentum, (float)eps);
+  } else {
+    const BnFinalizeArgs fin = {
+        weight.data_ptr<float>(), bias.data_ptr<float>(), rmean_p, rvar_p,
+        save_mean.data_ptr<float>(), save_invstd.data_ptr<float>(),
+        scale.data_ptr<float>(), biasf.data_ptr<float>(), g.M,
+        (float)momentum, (float)eps};
+    hipLaunchKernelGGL((bn_reduce_tile_kernel<KS_BN_RTILE, true>),
+                       dim3((g.C + KS_BN_RTILE - 1) / KS_BN_RTILE),
+                       dim3(64 * KS_BN_RTILE), 0, stream.stream(),
+                       part.data_ptr<float>(), g.stat_blocks, g.C,
+                       (float*)nullptr, (float*)nullptr, fin);
+  }
   auto launch_apply = [&](auto kern) {
     hipLaunchKernelGGL(kern, dim3(g.blocks), dim3(KS_BN_BLOCK), 0,
                        stream.stream(),
@@ -855,7 +1012,8 @@ std::vector<torch::Tensor> bn_relu_bwd(torch::Tensor x, torch::Tensor y,
                                        torch::Tensor bias, torch::Tensor mean,
                                        torch::Tensor invstd, bool need_dres,
                                        bool relu,
-                                       c10::optional<torch::Tensor> dy2) {
+                                       c10::optional<torch::Tensor> dy2,
+                                       bool legacy_reduce) {
   TORCH_CHECK(relu || !need_dres,
               "bn_relu_bwd: residual path requires the ReLU variant");
   Geom g = geom_of(x);
@@ -885,6 +1043,21 @@ std::vector<torch::Tensor> bn_relu_bwd(torch::Tensor x, torch::Tensor y,
   torch::Tensor dres;
   if (!dy.is_contiguous(at::MemoryFormat::ChannelsLast))
     dy = dy.contiguous(at::MemoryFormat::ChannelsLast);
+  // block partials -> dbias, dscale
+  auto launch_reduce = [&]() {
+    if (legacy_reduce) {
+      hipLaunchKernelGGL(bn_reduce_partials_kernel, dim3((g.C + 3) / 4),
+                         dim3(64, 4), 0, stream.stream(),
+                         part.data_ptr<float>(), g.stat_blocks, g.C, dbias_p,
+                         dscale_p);
+    } else {
+      hipLaunchKernelGGL((bn_reduce_tile_kernel<KS_BN_RTILE, false>),
+                         dim3((g.C + KS_BN_RTILE - 1) / KS_BN_RTILE),
+                         dim3(64 * KS_BN_RTILE), 0, stream.stream(),
+                         part.data_ptr<float>(), g.stat_blocks, g.C, dbias_p,
+                         dscale_p, BnFinalizeArgs{});
+    }
+  };
 
   if (need_dres) {
     // residual: the stats pass writes dym (= dres), the apply pass
@@ -905,10 +1078,7 @@ std::vector<torch::Tensor> bn_relu_bwd(torch::Tensor x, torch::Tensor y,
     };
     fold_dy2 ? launch_rstats(bn_bwd_stats_kernel<true, true>)
              : launch_rstats(bn_bwd_stats_kernel<true, false>);
-    hipLaunchKernelGGL(bn_reduce_partials_kernel,
-                       dim3((g.C + 3) / 4), dim3(64, 4), 0, stream.stream(),
-                       part.data_ptr<float>(), g.stat_blocks, g.C,
-                       dbias_p, dscale_p);
+    launch_reduce();
     hipLaunchKernelGGL(bn_bwd_apply_dym_kernel, dim3(g.blocks),
                        dim3(KS_BN_BLOCK), 0, stream.stream(),
                        reinterpret_cast<const ushort8*>(x.data_ptr()),
@@ -934,10 +1104,7 @@ std::vector<torch::Tensor> bn_relu_bwd(torch::Tensor x, torch::Tensor y,
   };
   relu ? launch_stats(bn_bwd_stats_noy_kernel<true>)
        : launch_stats(bn_bwd_stats_noy_kernel<false>);
-  hipLaunchKernelGGL(bn_reduce_partials_kernel,
-                     dim3((g.C + 3) / 4), dim3(64, 4), 0, stream.stream(),
-                     part.data_ptr<float>(), g.stat_blocks, g.C,
-                     dbias_p, dscale_p);
+  launch_reduce();
   auto launch_bapply = [&](auto kern) {
     hipLaunchKernelGGL(kern, dim3(g.blocks), dim3(KS_BN_BLOCK), 0,
                        stream.stream(),

@@ -14,8 +14,8 @@
 //  - sgd_mom_multi_f32_kernel: the same update for up to 110 tensors per
 //    launch; pointers and block prefix sums ride in the kernel arguments
 //    (ResNet50's 161 tensors: 2 launches instead of 161).
-//  - bn_relu.hip / pool.hip: fused NHWC bf16 BN+ReLU(+add) and max-pool
-//    (bound below).
+//  - bn_relu.hip / pool.hip / cast.hip: fused NHWC bf16 BN+ReLU(+add),
+//    max-pool and the multi-tensor f32 <-> bf16 casts (bound below).
 #include <hip/hip_runtime.h>
 #include <torch/extension.h>
 #include <ATen/cuda/CUDAContext.h>
@@ -313,7 +313,8 @@ int64_t sgd_momentum_multi_(std::vector<torch::Tensor> params,
 std::vector<torch::Tensor> bn_relu_fwd_train(
     torch::Tensor x, torch::Tensor weight, torch::Tensor bias,
     torch::Tensor running_mean, torch::Tensor running_var, double momentum,
-    double eps, c10::optional<torch::Tensor> res, bool relu);
+    double eps, c10::optional<torch::Tensor> res, bool relu,
+    bool legacy_reduce);
 torch::Tensor bn_relu_fwd_eval(torch::Tensor x, torch::Tensor weight,
                                torch::Tensor bias, torch::Tensor rmean,
                                torch::Tensor rvar, double eps,
@@ -323,7 +324,14 @@ std::vector<torch::Tensor> bn_relu_bwd(torch::Tensor x, torch::Tensor y,
                                        torch::Tensor bias, torch::Tensor mean,
                                        torch::Tensor invstd, bool need_dres,
                                        bool relu,
-                                       c10::optional<torch::Tensor> dy2);
+                                       c10::optional<torch::Tensor> dy2,
+                                       bool legacy_reduce);
+
+// multi-tensor f32 <-> bf16 casts (cast.hip)
+std::vector<c10::optional<torch::Tensor>> cast_f32_to_bf16_multi(
+    std::vector<c10::optional<torch::Tensor>> src);
+std::vector<c10::optional<torch::Tensor>> cast_bf16_to_f32_multi(
+    std::vector<c10::optional<torch::Tensor>> src);
 
 // fused NHWC bf16 max-pool, one-byte argmax + gather backward (pool.hip)
 std::vector<torch::Tensor> max_pool_nhwc_fwd(torch::Tensor x, int64_t k,
@@ -342,12 +350,20 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "fused SGD+momentum update of all tensors in as few launches as "
         "the kernel-argument limit allows; a None gradient skips its "
         "tensor; returns the number of launches");
-  m.def("bn_relu_fwd_train", &bn_relu_fwd_train);
+  m.def("bn_relu_fwd_train", &bn_relu_fwd_train, py::arg("x"),
+        py::arg("weight"), py::arg("bias"), py::arg("running_mean"),
+        py::arg("running_var"), py::arg("momentum"), py::arg("eps"),
+        py::arg("res"), py::arg("relu"), py::arg("legacy_reduce") = false);
   m.def("bn_relu_fwd_eval", &bn_relu_fwd_eval);
   m.def("bn_relu_bwd", &bn_relu_bwd, py::arg("x"), py::arg("y"),
         py::arg("dy"), py::arg("weight"), py::arg("bias"), py::arg("mean"),
         py::arg("invstd"), py::arg("need_dres"), py::arg("relu"),
-        py::arg("dy2") = py::none());
+        py::arg("dy2") = py::none(), py::arg("legacy_reduce") = false);
+  m.def("cast_f32_to_bf16_multi", &cast_f32_to_bf16_multi,
+        "f32 -> bf16 (torch rounding) of every tensor of a list in as few "
+        "launches as the kernel-argument limit allows; None stays None");
+  m.def("cast_bf16_to_f32_multi", &cast_bf16_to_f32_multi,
+        "bf16 -> f32 of every tensor of a list; None stays None");
   m.def("max_pool_nhwc_fwd", &max_pool_nhwc_fwd);
   m.def("max_pool_nhwc_bwd", &max_pool_nhwc_bwd);
 }
