@@ -149,7 +149,9 @@ class ResNet(nn.Module):
     def _forward(self, x):
         if self.fused_ops:
             from .. import ops
-            x = self.maxpool(ops.bn_relu(self.conv1(x), self.bn1))
+            # the pool module runs the stem's BN+ReLU itself, fused with
+            # the pool where it can (ops.bn_relu_pool)
+            x = self.maxpool(ops.PendingBNReLU(self.conv1(x), self.bn1))
             if ops.bn_fork_enabled():
                 # every block hands its output on as a pair, so the two
                 # gradients of a residual join reach the block's last BN

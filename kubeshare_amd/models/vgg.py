@@ -12,6 +12,10 @@ _CFG16 = [64, 64, "M", 128, 128, "M", 256, 256, 256, "M",
 
 class ConvBNReLU(nn.Module):
     fused_ops = False  # set by kubeshare_amd.ops.fuse_model
+    # set by VGG on the blocks directly in front of a pool: when fused,
+    # such a block leaves its BN+ReLU to the pool module
+    # (ops.PendingBNReLU -> ops.bn_relu_pool)
+    defer_to_pool = False
 
     def __init__(self, in_ch: int, out_ch: int):
         super().__init__()
@@ -22,6 +26,8 @@ class ConvBNReLU(nn.Module):
     def forward(self, x):
         if self.fused_ops:
             from .. import ops
+            if self.defer_to_pool:
+                return ops.PendingBNReLU(self.conv(x), self.bn)
             return ops.bn_relu(self.conv(x), self.bn)
         return self.relu(self.bn(self.conv(x)))
 
@@ -32,6 +38,7 @@ class VGG(nn.Module):
         layers, in_ch = [], 3
         for v in cfg:
             if v == "M":
+                layers[-1].defer_to_pool = True
                 layers.append(FusedMaxPool2d(2, 2))
             else:
                 layers.append(ConvBNReLU(in_ch, v))

@@ -14,6 +14,7 @@ _BUILD_DIR = os.path.join(_HERE, "_build")
 _SRCS = [os.path.join(_HERE, "hip", "ks_ops.hip"),
          os.path.join(_HERE, "hip", "bn_relu.hip"),
          os.path.join(_HERE, "hip", "pool.hip"),
+         os.path.join(_HERE, "hip", "bn_pool.hip"),
          os.path.join(_HERE, "hip", "cast.hip")]
 
 _ext = None
@@ -491,6 +492,122 @@ def max_pool_nhwc(x, kernel_size, stride=None, padding=0):
     want_idx = torch.is_grad_enabled() and x.requires_grad
     fn = _MaxPoolNHWCFn or _max_pool_autograd()
     return fn.apply(x, *cfg, want_idx)
+
+
+# ------------------------------------------- fused BN+ReLU+max-pool
+_BNReLUMaxPoolNHWCFn = None
+
+
+def bn_pool_enabled() -> bool:
+    """KUBESHARE_BN_POOL=0 runs BN+ReLU and the max-pool as two ops
+    (ops.bn_relu, then ops.max_pool_nhwc) wherever bn_relu_pool would
+    have fused them (A/B runs, operator escape hatch)."""
+    return os.environ.get("KUBESHARE_BN_POOL", "1") != "0"
+
+
+def bn_relu_pool_supported(x, kernel_size, stride=None, padding=0) -> bool:
+    """True when hip/bn_pool.hip covers BN+ReLU+max-pool of x: what both
+    bn_relu and max_pool_supported accept — channels-last bf16 on the
+    GPU, C % 8 == 0, 8 <= C <= 2048, (k, s, p) in (3, 2, 1) / (2, 2, 0),
+    a non-empty output and N*H*W below 2**31. (The BN output has x's
+    shape, so the pool's predicate is evaluated on x itself.)"""
+    return _pool_cfg_supported(x, _pool_cfg(kernel_size, stride, padding))
+
+
+def _bn_relu_pool_autograd():
+    """Lazily build the autograd.Function (torch import deferred)."""
+    global _BNReLUMaxPoolNHWCFn
+    if _BNReLUMaxPoolNHWCFn is not None:
+        return _BNReLUMaxPoolNHWCFn
+    import torch
+    from torch.autograd.function import once_differentiable
+
+    class BNReLUMaxPoolNHWCFn(torch.autograd.Function):
+        """max_pool(relu(batch_norm(x))) on NHWC bf16 via hip/bn_pool.hip.
+        The full-resolution BN output is never allocated: the forward
+        pools while it applies, and autograd keeps x, the one-byte
+        window codes and the per-channel vectors; the backward rebuilds
+        the pool gradient and the ReLU mask in registers. Values are
+        those of ops.max_pool_nhwc(ops.bn_relu(x, bn)), bit for bit in
+        forward."""
+
+        @staticmethod
+        def forward(ctx, x, weight, bias, running_mean, running_var,
+                    training, momentum, eps, k, s, p, want_idx):
+            ext = _load()
+            w32 = weight.float()
+            b32 = bias.float()
+            if not training:  # no gradients: bn_relu_pool sees to that
+                return ext.bn_relu_pool_fwd_eval(
+                    x, w32, b32, running_mean.float(), running_var.float(),
+                    eps, k, s, p)[0]
+            legacy = bn_reduce_legacy()
+            out = ext.bn_relu_pool_fwd_train(
+                x, w32, b32, running_mean, running_var, momentum, eps,
+                k, s, p, want_idx, legacy)
+            if want_idx:
+                ctx.save_for_backward(x, out[3], out[1], out[2], w32, b32)
+                ctx.cfg = (k, s, p)
+                ctx.wdtype = weight.dtype
+                ctx.legacy_reduce = legacy
+            return out[0]
+
+        @staticmethod
+        @once_differentiable
+        def backward(ctx, dy):
+            x, idx, mean, invstd, w32, b32 = ctx.saved_tensors
+            # y.sum().backward() hands over a stride-0 expanded dy
+            if not dy.is_contiguous(memory_format=torch.channels_last):
+                dy = dy.contiguous(memory_format=torch.channels_last)
+            dx, dscale, dbias = _load().bn_relu_pool_bwd(
+                x, dy, idx, w32, b32, mean, invstd, *ctx.cfg,
+                ctx.legacy_reduce)
+            return (dx, dscale.to(ctx.wdtype), dbias.to(ctx.wdtype)) + \
+                (None,) * 9
+
+    _BNReLUMaxPoolNHWCFn = BNReLUMaxPoolNHWCFn
+    return BNReLUMaxPoolNHWCFn
+
+
+def bn_relu_pool(x, bn, kernel_size, stride=None, padding=0):
+    """max_pool2d(relu(batch_norm(x))) as channels-last bf16 in one
+    fused op (hip/bn_pool.hip), using an nn.BatchNorm2d's parameters and
+    buffers exactly as bn_relu does; running statistics are updated in
+    training mode. Outside bn_relu_pool_supported, in eval mode with
+    gradients required, and under KUBESHARE_BN_POOL=0 it runs the
+    composition max_pool_nhwc(bn_relu(x, bn), ...), which has its own
+    eager fall-backs."""
+    import torch
+
+    cfg = _pool_cfg(kernel_size, stride, padding)
+    fused = bn_pool_enabled() and _pool_cfg_supported(x, cfg)
+    want_idx = False
+    if fused:
+        want_idx = torch.is_grad_enabled() and (
+            x.requires_grad or bn.weight.requires_grad
+            or bn.bias.requires_grad)
+        fused = bn.training or not want_idx
+    if not fused:
+        return max_pool_nhwc(bn_relu(x, bn), kernel_size, stride, padding)
+    fn = _BNReLUMaxPoolNHWCFn or _bn_relu_pool_autograd()
+    return fn.apply(x, bn.weight, bn.bias, bn.running_mean, bn.running_var,
+                    bn.training, bn.momentum, bn.eps, *cfg, want_idx)
+
+
+class PendingBNReLU:
+    """A BN+ReLU that has not run yet: the conv output x and its
+    nn.BatchNorm2d, handed to the FusedMaxPool2d that follows so that it
+    can fuse the three (bn_relu_pool). materialize() runs the BN+ReLU on
+    its own. Only fused models create one."""
+
+    __slots__ = ("x", "bn")
+
+    def __init__(self, x, bn):
+        self.x = x
+        self.bn = bn
+
+    def materialize(self):
+        return bn_relu(self.x, self.bn)
 
 
 def fuse_model(model):

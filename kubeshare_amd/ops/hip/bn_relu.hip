@@ -42,32 +42,10 @@
 
 #include <vector>
 
-typedef __attribute__((ext_vector_type(8))) unsigned short ushort8;
-typedef __attribute__((ext_vector_type(8))) float float8;
+// types, bf16 helpers, KS_BN_BLOCK / KS_BN_UNROLL, the pinned
+// per-element expressions and the host steps shared with bn_pool.hip
+#include "bn_common.h"
 
-__device__ __forceinline__ float bf16_to_f32(unsigned short u) {
-  union {
-    unsigned int i;
-    float f;
-  } v;
-  v.i = ((unsigned int)u) << 16;
-  return v.f;
-}
-
-__device__ __forceinline__ unsigned short f32_to_bf16(float f) {
-  union {
-    float f;
-    unsigned int i;
-  } v;
-  v.f = f;
-  // round-to-nearest-even (matches PyTorch's float->bf16 cast)
-  unsigned int lsb = (v.i >> 16) & 1;
-  v.i += 0x7fffu + lsb;
-  return (unsigned short)(v.i >> 16);
-}
-
-#define KS_BN_BLOCK 512
-#define KS_BN_UNROLL 4
 #define KS_BN_UNROLL_STATS 8
 // two-gradient bwd stats: rows loaded per sub-batch of a KS_BN_UNROLL
 // group (see bn_bwd_stats_kernel)
@@ -373,9 +351,9 @@ __global__ void bn_apply_relu_kernel(const ushort8* __restrict__ x,
     for (int u = 0; u < KS_BN_UNROLL; u++) {
 #pragma unroll
       for (int j = 0; j < 8; j++) {
-        float f = fmaf(bf16_to_f32(v[u][j]), s[j], b[j]);
+        float f = bn_affine(bf16_to_f32(v[u][j]), s[j], b[j]);
         if (WITH_RES) f += bf16_to_f32(r[u][j]);
-        o[u][j] = f32_to_bf16(RELU && f < 0.f ? 0.f : f);
+        o[u][j] = RELU ? bn_relu_bf16(f) : f32_to_bf16(f);
       }
       y[k[u]] = o[u];
     }
@@ -388,9 +366,9 @@ __global__ void bn_apply_relu_kernel(const ushort8* __restrict__ x,
     ushort8 o;
 #pragma unroll
     for (int j = 0; j < 8; j++) {
-      float f = fmaf(bf16_to_f32(v[j]), s[j], b[j]);
+      float f = bn_affine(bf16_to_f32(v[j]), s[j], b[j]);
       if (WITH_RES) f += bf16_to_f32(r[j]);
-      o[j] = f32_to_bf16(RELU && f < 0.f ? 0.f : f);
+      o[j] = RELU ? bn_relu_bf16(f) : f32_to_bf16(f);
     }
     y[k] = o;
   }
@@ -408,29 +386,7 @@ __device__ __forceinline__ float bn_join_grad(unsigned short a,
   return bf16_to_f32(f32_to_bf16(bf16_to_f32(a) + bf16_to_f32(b)));
 }
 
-// dscale accumulation, pinned. Left to -ffp-contract the backend fused
-// `ads += g * xhat` for some channels and rows and not for others (it
-// vectorises across rows for channels 6 and 7 of a four-row group), so
-// the sums depended on the unroll. The pattern is now explicit and is
-// the one every earlier build computed: within a whole group of four
-// rows channels 0-5 use an FMA and channels 6-7 a rounded product, then
-// an add; the leftover rows use an FMA for every channel. Any unroll
-// that keeps a lane's rows in order and in the same groups of four
-// therefore gives the same bits.
-__device__ __forceinline__ float bn_mul_add_unfused(float acc, float a,
-                                                    float b) {
-#pragma clang fp contract(off)
-  float prod = a * b;
-  return acc + prod;
-}
-
-template <bool GROUPED>
-__device__ __forceinline__ float bn_acc_dscale(float acc, float g, float xhat,
-                                               int j) {
-  return (GROUPED && j >= 6) ? bn_mul_add_unfused(acc, g, xhat)
-                             : fmaf(g, xhat, acc);
-}
-
+// (the pinned dscale accumulation, bn_acc_dscale, is in bn_common.h)
 template <bool WRITE_DYM, bool WITH_DY2 = false>
 __global__ void bn_bwd_stats_kernel(const ushort8* __restrict__ x,
                                     const ushort8* __restrict__ y,
@@ -872,19 +828,12 @@ __global__ void bn_fold_eval_kernel(const float* __restrict__ weight,
 }
 
 // ================================================================ host
-namespace {
-
-struct Geom {
-  long long M;
-  int C, CG, blocks, stat_blocks;
-};
-
-Geom geom_of(const torch::Tensor& x) {
+BnGeom bn_geom_of(const torch::Tensor& x) {
   TORCH_CHECK(x.dim() == 4, "bn_relu: 4D NCHW tensor expected");
   TORCH_CHECK(x.scalar_type() == at::kBFloat16, "bn_relu: bf16 only");
   TORCH_CHECK(x.is_contiguous(at::MemoryFormat::ChannelsLast),
               "bn_relu: channels-last only");
-  Geom g;
+  BnGeom g;
   g.C = (int)x.size(1);
   TORCH_CHECK(g.C % 8 == 0 && g.C <= KS_BN_BLOCK * 8,
               "bn_relu: C must be a multiple of 8 and <= 8*KS_BN_BLOCK");
@@ -899,40 +848,28 @@ Geom geom_of(const torch::Tensor& x) {
   return g;
 }
 
-}  // namespace
-
-std::vector<torch::Tensor> bn_relu_fwd_train(
-    torch::Tensor x, torch::Tensor weight, torch::Tensor bias,
-    torch::Tensor running_mean, torch::Tensor running_var, double momentum,
-    double eps, c10::optional<torch::Tensor> res, bool relu,
-    bool legacy_reduce) {
-  Geom g = geom_of(x);
-  auto stream = at::cuda::getCurrentCUDAStream();
+void bn_launch_fwd_stats(const torch::Tensor& x, const BnGeom& g,
+                         const torch::Tensor& weight,
+                         const torch::Tensor& bias, float* rmean_p,
+                         float* rvar_p, torch::Tensor& save_mean,
+                         torch::Tensor& save_invstd, torch::Tensor& scale,
+                         torch::Tensor& biasf, double momentum, double eps,
+                         bool legacy_reduce, hipStream_t stream) {
   auto f32 = x.options().dtype(at::kFloat);
   auto part = at::empty({(long long)2 * g.stat_blocks * g.C}, f32);
-  auto y = at::empty_like(x);
-  auto save_mean = at::empty({g.C}, f32);
-  auto save_invstd = at::empty({g.C}, f32);
-  auto scale = at::empty({g.C}, f32);
-  auto biasf = at::empty({g.C}, f32);
-  float* rmean_p =
-      running_mean.defined() ? running_mean.data_ptr<float>() : nullptr;
-  float* rvar_p =
-      running_var.defined() ? running_var.data_ptr<float>() : nullptr;
-
   hipLaunchKernelGGL(bn_stats_kernel, dim3(g.stat_blocks),
-                     dim3(KS_BN_BLOCK), 0, stream.stream(),
+                     dim3(KS_BN_BLOCK), 0, stream,
                      reinterpret_cast<const ushort8*>(x.data_ptr()),
                      part.data_ptr<float>(), g.M, g.CG);
   if (legacy_reduce) {
     auto sums = at::empty({2 * g.C}, f32);
     hipLaunchKernelGGL(bn_reduce_partials_kernel,
-                       dim3((g.C + 3) / 4), dim3(64, 4), 0, stream.stream(),
+                       dim3((g.C + 3) / 4), dim3(64, 4), 0, stream,
                        part.data_ptr<float>(), g.stat_blocks, g.C,
                        sums.data_ptr<float>(), sums.data_ptr<float>() + g.C);
     int fb = (g.C + 255) / 256;
     hipLaunchKernelGGL(bn_finalize_kernel, dim3(fb), dim3(256), 0,
-                       stream.stream(), sums.data_ptr<float>(),
+                       stream, sums.data_ptr<float>(),
                        sums.data_ptr<float>() + g.C,
                        weight.data_ptr<float>(), bias.data_ptr<float>(),
                        rmean_p, rvar_p, save_mean.data_ptr<float>(),
@@ -947,10 +884,60 @@ std::vector<torch::Tensor> bn_relu_fwd_train(
         (float)momentum, (float)eps};
     hipLaunchKernelGGL((bn_reduce_tile_kernel<KS_BN_RTILE, true>),
                        dim3((g.C + KS_BN_RTILE - 1) / KS_BN_RTILE),
-                       dim3(64 * KS_BN_RTILE), 0, stream.stream(),
+                       dim3(64 * KS_BN_RTILE), 0, stream,
                        part.data_ptr<float>(), g.stat_blocks, g.C,
                        (float*)nullptr, (float*)nullptr, fin);
   }
+}
+
+void bn_launch_bwd_reduce(const float* part, int nblocks, int C, float* out0,
+                          float* out1, bool legacy_reduce,
+                          hipStream_t stream) {
+  if (legacy_reduce) {
+    hipLaunchKernelGGL(bn_reduce_partials_kernel, dim3((C + 3) / 4),
+                       dim3(64, 4), 0, stream, part, nblocks, C, out0, out1);
+  } else {
+    hipLaunchKernelGGL((bn_reduce_tile_kernel<KS_BN_RTILE, false>),
+                       dim3((C + KS_BN_RTILE - 1) / KS_BN_RTILE),
+                       dim3(64 * KS_BN_RTILE), 0, stream, part, nblocks, C,
+                       out0, out1, BnFinalizeArgs{});
+  }
+}
+
+void bn_launch_fold_eval(const torch::Tensor& weight,
+                         const torch::Tensor& bias,
+                         const torch::Tensor& rmean,
+                         const torch::Tensor& rvar, torch::Tensor& scale,
+                         torch::Tensor& biasf, int C, double eps,
+                         hipStream_t stream) {
+  int fb = (C + 255) / 256;
+  hipLaunchKernelGGL(bn_fold_eval_kernel, dim3(fb), dim3(256), 0, stream,
+                     weight.data_ptr<float>(), bias.data_ptr<float>(),
+                     rmean.data_ptr<float>(), rvar.data_ptr<float>(),
+                     scale.data_ptr<float>(), biasf.data_ptr<float>(), C,
+                     (float)eps);
+}
+
+std::vector<torch::Tensor> bn_relu_fwd_train(
+    torch::Tensor x, torch::Tensor weight, torch::Tensor bias,
+    torch::Tensor running_mean, torch::Tensor running_var, double momentum,
+    double eps, c10::optional<torch::Tensor> res, bool relu,
+    bool legacy_reduce) {
+  BnGeom g = bn_geom_of(x);
+  auto stream = at::cuda::getCurrentCUDAStream();
+  auto f32 = x.options().dtype(at::kFloat);
+  auto y = at::empty_like(x);
+  auto save_mean = at::empty({g.C}, f32);
+  auto save_invstd = at::empty({g.C}, f32);
+  auto scale = at::empty({g.C}, f32);
+  auto biasf = at::empty({g.C}, f32);
+  float* rmean_p =
+      running_mean.defined() ? running_mean.data_ptr<float>() : nullptr;
+  float* rvar_p =
+      running_var.defined() ? running_var.data_ptr<float>() : nullptr;
+  bn_launch_fwd_stats(x, g, weight, bias, rmean_p, rvar_p, save_mean,
+                      save_invstd, scale, biasf, momentum, eps, legacy_reduce,
+                      stream.stream());
   auto launch_apply = [&](auto kern) {
     hipLaunchKernelGGL(kern, dim3(g.blocks), dim3(KS_BN_BLOCK), 0,
                        stream.stream(),
@@ -975,18 +962,14 @@ torch::Tensor bn_relu_fwd_eval(torch::Tensor x, torch::Tensor weight,
                                torch::Tensor bias, torch::Tensor rmean,
                                torch::Tensor rvar, double eps,
                                c10::optional<torch::Tensor> res, bool relu) {
-  Geom g = geom_of(x);
+  BnGeom g = bn_geom_of(x);
   auto stream = at::cuda::getCurrentCUDAStream();
   auto f32 = x.options().dtype(at::kFloat);
   auto scale = at::empty({g.C}, f32);
   auto biasf = at::empty({g.C}, f32);
   auto y = at::empty_like(x);
-  int fb = (g.C + 255) / 256;
-  hipLaunchKernelGGL(bn_fold_eval_kernel, dim3(fb), dim3(256), 0,
-                     stream.stream(), weight.data_ptr<float>(),
-                     bias.data_ptr<float>(), rmean.data_ptr<float>(),
-                     rvar.data_ptr<float>(), scale.data_ptr<float>(),
-                     biasf.data_ptr<float>(), g.C, (float)eps);
+  bn_launch_fold_eval(weight, bias, rmean, rvar, scale, biasf, g.C, eps,
+                      stream.stream());
   auto launch_apply = [&](auto kern) {
     hipLaunchKernelGGL(kern, dim3(g.blocks), dim3(KS_BN_BLOCK), 0,
                        stream.stream(),
@@ -1016,7 +999,7 @@ std::vector<torch::Tensor> bn_relu_bwd(torch::Tensor x, torch::Tensor y,
                                        bool legacy_reduce) {
   TORCH_CHECK(relu || !need_dres,
               "bn_relu_bwd: residual path requires the ReLU variant");
-  Geom g = geom_of(x);
+  BnGeom g = bn_geom_of(x);
   TORCH_CHECK(dy.sizes() == x.sizes() && y.sizes() == x.sizes() &&
                   dy.scalar_type() == at::kBFloat16,
               "bn_relu_bwd: dy must be bf16 of x's shape");
@@ -1045,18 +1028,8 @@ std::vector<torch::Tensor> bn_relu_bwd(torch::Tensor x, torch::Tensor y,
     dy = dy.contiguous(at::MemoryFormat::ChannelsLast);
   // block partials -> dbias, dscale
   auto launch_reduce = [&]() {
-    if (legacy_reduce) {
-      hipLaunchKernelGGL(bn_reduce_partials_kernel, dim3((g.C + 3) / 4),
-                         dim3(64, 4), 0, stream.stream(),
-                         part.data_ptr<float>(), g.stat_blocks, g.C, dbias_p,
-                         dscale_p);
-    } else {
-      hipLaunchKernelGGL((bn_reduce_tile_kernel<KS_BN_RTILE, false>),
-                         dim3((g.C + KS_BN_RTILE - 1) / KS_BN_RTILE),
-                         dim3(64 * KS_BN_RTILE), 0, stream.stream(),
-                         part.data_ptr<float>(), g.stat_blocks, g.C, dbias_p,
-                         dscale_p, BnFinalizeArgs{});
-    }
+    bn_launch_bwd_reduce(part.data_ptr<float>(), g.stat_blocks, g.C, dbias_p,
+                         dscale_p, legacy_reduce, stream.stream());
   };
 
   if (need_dres) {

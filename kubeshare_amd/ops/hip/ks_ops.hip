@@ -16,6 +16,8 @@
 //    (ResNet50's 161 tensors: 2 launches instead of 161).
 //  - bn_relu.hip / pool.hip / cast.hip: fused NHWC bf16 BN+ReLU(+add),
 //    max-pool and the multi-tensor f32 <-> bf16 casts (bound below).
+//  - bn_pool.hip: BN+ReLU+max-pool in one op, the full-resolution
+//    activation never written (ResNet stem, VGG pools).
 #include <hip/hip_runtime.h>
 #include <torch/extension.h>
 #include <ATen/cuda/CUDAContext.h>
@@ -341,6 +343,22 @@ torch::Tensor max_pool_nhwc_bwd(torch::Tensor dy, torch::Tensor idx,
                                 std::vector<int64_t> input_sizes, int64_t k,
                                 int64_t s, int64_t p);
 
+// fused NHWC bf16 BN+ReLU+max-pool, recomputing backward (bn_pool.hip)
+std::vector<torch::Tensor> bn_relu_pool_fwd_train(
+    torch::Tensor x, torch::Tensor weight, torch::Tensor bias,
+    torch::Tensor running_mean, torch::Tensor running_var, double momentum,
+    double eps, int64_t k, int64_t s, int64_t p, bool want_idx,
+    bool legacy_reduce);
+std::vector<torch::Tensor> bn_relu_pool_fwd_eval(
+    torch::Tensor x, torch::Tensor weight, torch::Tensor bias,
+    torch::Tensor rmean, torch::Tensor rvar, double eps, int64_t k,
+    int64_t s, int64_t p);
+std::vector<torch::Tensor> bn_relu_pool_bwd(
+    torch::Tensor x, torch::Tensor dy, torch::Tensor idx,
+    torch::Tensor weight, torch::Tensor bias, torch::Tensor mean,
+    torch::Tensor invstd, int64_t k, int64_t s, int64_t p,
+    bool legacy_reduce);
+
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("burn", &burn, "occupy the GPU for ~ms milliseconds",
         py::arg("ms"), py::arg("blocks") = 1024, py::arg("threads") = 256);
@@ -366,4 +384,16 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "bf16 -> f32 of every tensor of a list; None stays None");
   m.def("max_pool_nhwc_fwd", &max_pool_nhwc_fwd);
   m.def("max_pool_nhwc_bwd", &max_pool_nhwc_bwd);
+  m.def("bn_relu_pool_fwd_train", &bn_relu_pool_fwd_train, py::arg("x"),
+        py::arg("weight"), py::arg("bias"), py::arg("running_mean"),
+        py::arg("running_var"), py::arg("momentum"), py::arg("eps"),
+        py::arg("k"), py::arg("s"), py::arg("p"), py::arg("want_idx"),
+        py::arg("legacy_reduce") = false,
+        "{y, mean, invstd} and, with want_idx, the one-byte window codes");
+  m.def("bn_relu_pool_fwd_eval", &bn_relu_pool_fwd_eval,
+        "{y} from the running statistics; no codes");
+  m.def("bn_relu_pool_bwd", &bn_relu_pool_bwd, py::arg("x"), py::arg("dy"),
+        py::arg("idx"), py::arg("weight"), py::arg("bias"), py::arg("mean"),
+        py::arg("invstd"), py::arg("k"), py::arg("s"), py::arg("p"),
+        py::arg("legacy_reduce") = false, "{dx, dscale, dbias}");
 }
