@@ -76,7 +76,8 @@ def dump_outputs(dump_dir: str, name: str, loss, logits, params):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--model", default="resnet50",
-                    choices=["resnet18", "resnet50", "vgg16"],
+                    choices=["resnet18", "resnet50", "vgg16",
+                             "vgg16_plain"],
                     help="ImageNet-shaped families only (the mnist/"
                          "lstm families have their own input shapes — "
                          "see models.small.synthetic_batch)")

@@ -15,6 +15,7 @@ _SRCS = [os.path.join(_HERE, "hip", "ks_ops.hip"),
          os.path.join(_HERE, "hip", "bn_relu.hip"),
          os.path.join(_HERE, "hip", "pool.hip"),
          os.path.join(_HERE, "hip", "bn_pool.hip"),
+         os.path.join(_HERE, "hip", "bias_relu.hip"),
          os.path.join(_HERE, "hip", "cast.hip")]
 
 _ext = None
@@ -594,6 +595,159 @@ def bn_relu_pool(x, bn, kernel_size, stride=None, padding=0):
                     bn.training, bn.momentum, bn.eps, *cfg, want_idx)
 
 
+# --------------------------------------- fused bias+ReLU(+max-pool)
+_BiasReLUFn = None
+_BiasReLUMaxPoolNHWCFn = None
+
+
+def bias_relu_enabled() -> bool:
+    """KUBESHARE_BIAS_RELU=0 routes flagged BN-free models
+    (models.vgg.VGGPlain) back to their stock modules (A/B runs,
+    operator escape hatch). KUBESHARE_FUSED_POOL=0 keeps its meaning:
+    the pools then run the stock module and only bias+ReLU is fused."""
+    return os.environ.get("KUBESHARE_BIAS_RELU", "1") != "0"
+
+
+def bias_relu_supported(x) -> bool:
+    """True when hip/bias_relu.hip covers bias+ReLU of x: channels-last
+    bf16 on the GPU, C % 8 == 0, 8 <= C <= 2048, not empty and N*H*W
+    below 2**31 (bias_relu_pool_supported minus the pool geometry)."""
+    import torch
+
+    if x.dim() != 4:
+        return False
+    n, c, h, w = x.shape
+    return (x.is_cuda and x.dtype == torch.bfloat16
+            and c % 8 == 0 and 8 <= c <= 2048
+            and n >= 1 and h >= 1 and w >= 1 and n * h * w < 2 ** 31
+            and x.is_contiguous(memory_format=torch.channels_last))
+
+
+def bias_relu_pool_supported(x, kernel_size, stride=None, padding=0) -> bool:
+    """True when hip/bias_relu.hip covers bias+ReLU+max-pool of x: what
+    bias_relu_supported and max_pool_supported both accept ((k, s, p) in
+    (3, 2, 1) / (2, 2, 0) and a non-empty output)."""
+    return _pool_cfg_supported(x, _pool_cfg(kernel_size, stride, padding))
+
+
+def _bias_relu_autograd():
+    """Lazily build the autograd.Function (torch import deferred)."""
+    global _BiasReLUFn
+    if _BiasReLUFn is not None:
+        return _BiasReLUFn
+    import torch
+    from torch.autograd.function import once_differentiable
+
+    class BiasReLUFn(torch.autograd.Function):
+        """y = bf16(relu(f32(x) + bias)) on NHWC bf16 via
+        hip/bias_relu.hip, out of place. Autograd keeps ONLY y; the
+        backward writes dx = (y > 0 ? dy : 0) and sums it into the bias
+        gradient in the same pass."""
+
+        @staticmethod
+        def forward(ctx, x, bias):
+            y = _load().bias_relu_fwd(
+                x, bias.detach().float().contiguous())
+            ctx.save_for_backward(y)
+            ctx.bdtype = bias.dtype
+            return y
+
+        @staticmethod
+        @once_differentiable
+        def backward(ctx, dy):
+            (y,) = ctx.saved_tensors
+            # y.sum().backward() hands over a stride-0 expanded dy
+            if not dy.is_contiguous(memory_format=torch.channels_last):
+                dy = dy.contiguous(memory_format=torch.channels_last)
+            dx, db = _load().bias_relu_bwd(dy, y)
+            return dx, db.to(ctx.bdtype)
+
+    _BiasReLUFn = BiasReLUFn
+    return BiasReLUFn
+
+
+def _bias_relu_pool_autograd():
+    """Lazily build the autograd.Function (torch import deferred)."""
+    global _BiasReLUMaxPoolNHWCFn
+    if _BiasReLUMaxPoolNHWCFn is not None:
+        return _BiasReLUMaxPoolNHWCFn
+    import torch
+    from torch.autograd.function import once_differentiable
+
+    class BiasReLUMaxPoolNHWCFn(torch.autograd.Function):
+        """max_pool(relu(x + bias)) on NHWC bf16 via hip/bias_relu.hip.
+        The full-resolution activation is never allocated. Autograd
+        keeps ONLY the one-byte window codes and the pooled y (the map
+        is monotone per channel, so the pooled y is the selected
+        element's value and carries its ReLU mask), and nothing at all
+        when no gradient is required."""
+
+        @staticmethod
+        def forward(ctx, x, bias, k, s, p, want_idx):
+            out = _load().bias_relu_pool_fwd(
+                x, bias.detach().float().contiguous(), k, s, p, want_idx)
+            if want_idx:
+                ctx.save_for_backward(out[1], out[0])
+                ctx.input_sizes = list(x.shape)
+                ctx.cfg = (k, s, p)
+                ctx.bdtype = bias.dtype
+            return out[0]
+
+        @staticmethod
+        @once_differentiable
+        def backward(ctx, dy):
+            idx, y = ctx.saved_tensors
+            # y.sum().backward() hands over a stride-0 expanded dy
+            if not dy.is_contiguous(memory_format=torch.channels_last):
+                dy = dy.contiguous(memory_format=torch.channels_last)
+            dx, db = _load().bias_relu_pool_bwd(dy, idx, y, ctx.input_sizes,
+                                                *ctx.cfg)
+            return dx, db.to(ctx.bdtype), None, None, None, None
+
+    _BiasReLUMaxPoolNHWCFn = BiasReLUMaxPoolNHWCFn
+    return BiasReLUMaxPoolNHWCFn
+
+
+def bias_relu(x, bias):
+    """relu(x + bias[None, :, None, None]) for a conv output x (N, C, H,
+    W) and a per-channel bias (C), in one kernel each way
+    (hip/bias_relu.hip) where bias_relu_supported(x) holds:
+    y = bf16(relu(f32(x) + f32(bias))). The bias is added in f32 and is
+    NOT rounded to bf16 first; that is the one difference from the stock
+    autocast modules (a biased conv followed by nn.ReLU), which round
+    the bias to bf16 before adding it. Anything else runs the eager
+    expression torch.relu(x + bias.to(x.dtype).view(1, -1, 1, 1))."""
+    import torch
+
+    if not bias_relu_supported(x) or not bias.is_cuda:
+        return torch.relu(x + bias.to(x.dtype).view(1, -1, 1, 1))
+    fn = _BiasReLUFn or _bias_relu_autograd()
+    return fn.apply(x, bias)
+
+
+def bias_relu_pool(x, bias, kernel_size, stride=None, padding=0):
+    """max_pool2d(relu(x + bias)) as one fused op (hip/bias_relu.hip)
+    where bias_relu_pool_supported holds; values and gradients are those
+    of max_pool_nhwc(bias_relu(x, bias), ...), bit for bit. Outside that
+    predicate but inside bias_relu_supported it runs exactly that
+    composition; outside both, the eager expression of bias_relu
+    followed by F.max_pool2d."""
+    import torch
+
+    cfg = _pool_cfg(kernel_size, stride, padding)
+    if not _pool_cfg_supported(x, cfg) or not bias.is_cuda:
+        if bias_relu_supported(x) and bias.is_cuda:
+            return max_pool_nhwc(bias_relu(x, bias), kernel_size, stride,
+                                 padding)
+        y = torch.relu(x + bias.to(x.dtype).view(1, -1, 1, 1))
+        return torch.nn.functional.max_pool2d(y, kernel_size, stride,
+                                              padding)
+    want_idx = torch.is_grad_enabled() and (x.requires_grad
+                                            or bias.requires_grad)
+    fn = _BiasReLUMaxPoolNHWCFn or _bias_relu_pool_autograd()
+    return fn.apply(x, bias, *cfg, want_idx)
+
+
 class PendingBNReLU:
     """A BN+ReLU that has not run yet: the conv output x and its
     nn.BatchNorm2d, handed to the FusedMaxPool2d that follows so that it
@@ -614,7 +768,8 @@ def fuse_model(model):
     """Enable the fused BN+ReLU(+add) and max-pool paths on
     kubeshare_amd models (blocks and pool modules check their
     `fused_ops` flag; a flagged ResNet also stages its conv weights,
-    see stage_lowp_weights); verifies the extension
+    see stage_lowp_weights; a flagged VGGPlain runs bias_relu /
+    bias_relu_pool after its bias-free convs); verifies the extension
     is importable first (fail-loud on GPU boxes)."""
     _load()
     for m in model.modules():

@@ -98,6 +98,12 @@ void bn_launch_bwd_reduce(const float* part, int nblocks, int C, float* out0,
                           float* out1, bool legacy_reduce,
                           hipStream_t stream);
 
+// Block partials part[nblocks][C] -> out[C]: the one-output form of
+// bn_reduce_tile_kernel<.., false> (same summation contract, half the
+// loads of the two-slot form).
+void bn_launch_reduce_one(const float* part, int nblocks, int C, float* out,
+                          hipStream_t stream);
+
 // Eval mode: scale' and bias' from the running statistics
 // (bn_fold_eval_kernel).
 void bn_launch_fold_eval(const torch::Tensor& weight,

@@ -218,6 +218,9 @@ __device__ __forceinline__ void bn_finalize_channel(const BnFinalizeArgs& f,
 // shuffles in which lane = L*QC + q carries channel wave*QC + q.
 // FINALIZE: the lanes that end up with a channel's two sums go straight
 // on to bn_finalize_channel (no `sums` buffer, no finalize launch).
+// TWO=false: `part` has one half only (part[nblocks][C] -> out0[C]); the
+// second half's loads, shuffles and store are compiled out, the first
+// half's sum is the same (bias_relu.hip's bias gradient).
 // Swept in the ResNet50 bs256 step (average us per call, forward /
 // backward): TILE 16 x 8 loads 7.5 / 6.8, TILE 16 x 16 loads 7.8 / 6.9,
 // TILE 8 x 8 loads 7.9 / 7.0 — flat; what is left is mostly the cost
@@ -225,7 +228,7 @@ __device__ __forceinline__ void bn_finalize_channel(const BnFinalizeArgs& f,
 #define KS_BN_RTILE 16
 #define KS_BN_RLOADS 8  // independent loads in flight per half and thread
 
-template <int TILE, bool FINALIZE>
+template <int TILE, bool FINALIZE, bool TWO = true>
 __global__ void __launch_bounds__(64 * TILE)
 bn_reduce_tile_kernel(const float* __restrict__ part, int nblocks, int C,
                       float* __restrict__ out0, float* __restrict__ out1,
@@ -233,6 +236,7 @@ bn_reduce_tile_kernel(const float* __restrict__ part, int nblocks, int C,
   constexpr int NW = TILE;       // waves per block
   constexpr int QC = 64 / NW;    // channels per wave in the second stage
   static_assert(TILE == 8 || TILE == 16, "64 % TILE, 64 * TILE <= 1024");
+  static_assert(TWO || !FINALIZE, "the finalize math needs both sums");
   __shared__ float s_a[2][NW][TILE];
   const int tid = threadIdx.x;
   const int lane = tid & 63;
@@ -251,35 +255,35 @@ bn_reduce_tile_kernel(const float* __restrict__ part, int nblocks, int C,
       const int b = b0 + 64 * u;
       const bool ok = valid && b < nblocks;
       v0[u] = ok ? p0[(long long)b * C] : 0.f;
-      v1[u] = ok ? p1[(long long)b * C] : 0.f;
+      if (TWO) v1[u] = ok ? p1[(long long)b * C] : 0.f;
     }
 #pragma unroll
     for (int u = 0; u < KS_BN_RLOADS; u++)
       if (b0 + 64 * u < nblocks) {
         a0 += v0[u];
-        a1 += v1[u];
+        if (TWO) a1 += v1[u];
       }
   }
   // tree steps 32 .. NW inside the wave
 #pragma unroll
   for (int off = 32; off >= NW; off >>= 1) {
     a0 += __shfl_down(a0, off / NW * TILE, 64);
-    a1 += __shfl_down(a1, off / NW * TILE, 64);
+    if (TWO) a1 += __shfl_down(a1, off / NW * TILE, 64);
   }
   if (lane < TILE) {  // L == w: a[0 .. NW-1] of channel cc
     s_a[0][w][cc] = a0;
-    s_a[1][w][cc] = a1;
+    if (TWO) s_a[1][w][cc] = a1;
   }
   __syncthreads();
   if (tid >= 64 * (TILE / QC)) return;  // whole waves leave
   const int l2 = lane / QC;             // 0 .. NW-1
   const int cc2 = w * QC + lane % QC;
   a0 = s_a[0][l2][cc2];
-  a1 = s_a[1][l2][cc2];
+  if (TWO) a1 = s_a[1][l2][cc2];
 #pragma unroll
   for (int off = NW / 2; off > 0; off >>= 1) {
     a0 += __shfl_down(a0, off * QC, 64);
-    a1 += __shfl_down(a1, off * QC, 64);
+    if (TWO) a1 += __shfl_down(a1, off * QC, 64);
   }
   const int c2 = blockIdx.x * TILE + cc2;
   if (l2 != 0 || c2 >= C) return;
@@ -287,7 +291,7 @@ bn_reduce_tile_kernel(const float* __restrict__ part, int nblocks, int C,
     bn_finalize_channel(fin, c2, a0, a1);
   } else {
     out0[c2] = a0;
-    out1[c2] = a1;
+    if (TWO) out1[c2] = a1;
   }
 }
 
@@ -902,6 +906,14 @@ void bn_launch_bwd_reduce(const float* part, int nblocks, int C, float* out0,
                        dim3(64 * KS_BN_RTILE), 0, stream, part, nblocks, C,
                        out0, out1, BnFinalizeArgs{});
   }
+}
+
+void bn_launch_reduce_one(const float* part, int nblocks, int C, float* out,
+                          hipStream_t stream) {
+  hipLaunchKernelGGL((bn_reduce_tile_kernel<KS_BN_RTILE, false, false>),
+                     dim3((C + KS_BN_RTILE - 1) / KS_BN_RTILE),
+                     dim3(64 * KS_BN_RTILE), 0, stream, part, nblocks, C, out,
+                     (float*)nullptr, BnFinalizeArgs{});
 }
 
 void bn_launch_fold_eval(const torch::Tensor& weight,

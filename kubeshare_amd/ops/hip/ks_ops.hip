@@ -18,6 +18,8 @@
 //    max-pool and the multi-tensor f32 <-> bf16 casts (bound below).
 //  - bn_pool.hip: BN+ReLU+max-pool in one op, the full-resolution
 //    activation never written (ResNet stem, VGG pools).
+//  - bias_relu.hip: bias+ReLU(+max-pool) for conv layers without a BN
+//    (the plain VGG16), bias gradient in the same backward pass.
 #include <hip/hip_runtime.h>
 #include <torch/extension.h>
 #include <ATen/cuda/CUDAContext.h>
@@ -359,6 +361,17 @@ std::vector<torch::Tensor> bn_relu_pool_bwd(
     torch::Tensor invstd, int64_t k, int64_t s, int64_t p,
     bool legacy_reduce);
 
+// fused NHWC bf16 bias+ReLU(+max-pool) (bias_relu.hip)
+torch::Tensor bias_relu_fwd(torch::Tensor x, torch::Tensor bias);
+std::vector<torch::Tensor> bias_relu_bwd(torch::Tensor dy, torch::Tensor y);
+std::vector<torch::Tensor> bias_relu_pool_fwd(torch::Tensor x,
+                                              torch::Tensor bias, int64_t k,
+                                              int64_t s, int64_t p,
+                                              bool want_idx);
+std::vector<torch::Tensor> bias_relu_pool_bwd(
+    torch::Tensor dy, torch::Tensor idx, torch::Tensor y,
+    std::vector<int64_t> input_sizes, int64_t k, int64_t s, int64_t p);
+
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("burn", &burn, "occupy the GPU for ~ms milliseconds",
         py::arg("ms"), py::arg("blocks") = 1024, py::arg("threads") = 256);
@@ -396,4 +409,15 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("idx"), py::arg("weight"), py::arg("bias"), py::arg("mean"),
         py::arg("invstd"), py::arg("k"), py::arg("s"), py::arg("p"),
         py::arg("legacy_reduce") = false, "{dx, dscale, dbias}");
+  m.def("bias_relu_fwd", &bias_relu_fwd, py::arg("x"), py::arg("bias"),
+        "y = bf16(relu(f32(x) + bias)), bias f32");
+  m.def("bias_relu_bwd", &bias_relu_bwd, py::arg("dy"), py::arg("y"),
+        "{dx, db}");
+  m.def("bias_relu_pool_fwd", &bias_relu_pool_fwd, py::arg("x"),
+        py::arg("bias"), py::arg("k"), py::arg("s"), py::arg("p"),
+        py::arg("want_idx"),
+        "{y} and, with want_idx, the one-byte window codes");
+  m.def("bias_relu_pool_bwd", &bias_relu_pool_bwd, py::arg("dy"),
+        py::arg("idx"), py::arg("y"), py::arg("input_sizes"), py::arg("k"),
+        py::arg("s"), py::arg("p"), "{dx, db}");
 }
