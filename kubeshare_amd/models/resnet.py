@@ -47,13 +47,17 @@ class Bottleneck(nn.Module):
         x, x_id = x if pair else (x, x)
         if self.fused_ops:
             from .. import ops
-            # downsample BN has no activation: fused no-ReLU variant
-            # (otherwise it falls back to MIOpen's fp32 spatial BN)
-            identity = x_id if self.down is None else \
-                ops.bn_relu(self.down[0](x_id), self.down[1], relu=False)
+            # the downsample BN has no activation and only the join
+            # reads it: ops.bn_join runs both BNs, the add and the ReLU
+            # as one op (or as two bn_relu calls where it cannot)
+            if self.down is not None:
+                x_d = self.down[0](x_id)
             out = ops.bn_relu(self.conv1(x), self.bn1)
             out = ops.bn_relu(self.conv2(out), self.bn2)
-            return ops.bn_relu(self.conv3(out), self.bn3, res=identity,
+            if self.down is not None:
+                return ops.bn_join(self.conv3(out), self.bn3, x_d,
+                                   self.down[1], fork=pair)
+            return ops.bn_relu(self.conv3(out), self.bn3, res=x_id,
                                fork=pair)
         identity = x_id if self.down is None else self.down(x_id)
         out = self.relu(self.bn1(self.conv1(x)))
@@ -87,10 +91,13 @@ class BasicBlock(nn.Module):
         x, x_id = x if pair else (x, x)
         if self.fused_ops:
             from .. import ops
-            identity = x_id if self.down is None else \
-                ops.bn_relu(self.down[0](x_id), self.down[1], relu=False)
+            if self.down is not None:  # see Bottleneck.forward
+                x_d = self.down[0](x_id)
             out = ops.bn_relu(self.conv1(x), self.bn1)
-            return ops.bn_relu(self.conv2(out), self.bn2, res=identity,
+            if self.down is not None:
+                return ops.bn_join(self.conv2(out), self.bn2, x_d,
+                                   self.down[1], fork=pair)
+            return ops.bn_relu(self.conv2(out), self.bn2, res=x_id,
                                fork=pair)
         identity = x_id if self.down is None else self.down(x_id)
         out = self.relu(self.bn1(self.conv1(x)))

@@ -15,6 +15,7 @@ _SRCS = [os.path.join(_HERE, "hip", "ks_ops.hip"),
          os.path.join(_HERE, "hip", "bn_relu.hip"),
          os.path.join(_HERE, "hip", "pool.hip"),
          os.path.join(_HERE, "hip", "bn_pool.hip"),
+         os.path.join(_HERE, "hip", "bn_join.hip"),
          os.path.join(_HERE, "hip", "bias_relu.hip"),
          os.path.join(_HERE, "hip", "cast.hip")]
 
@@ -208,7 +209,13 @@ def _bn_relu_autograd():
         a separate bf16 add kernel whose result that kernel re-reads.
         Nothing on the fused path writes in place into y or y2; an
         in-place op on either would corrupt the other consumer's input,
-        so keep it that way."""
+        so keep it that way.
+
+        A residual BN in training mode saves the ReLU mask as bits (one
+        byte per 8 channels, written by the forward apply kernel)
+        instead of y: its backward stats kernel then reads 1/16 of a
+        pass where it read a whole one, for the same bits out.
+        KUBESHARE_BN_MASK=0 (see bn_mask_enabled) keeps y."""
 
         @staticmethod
         def forward(ctx, x, res, weight, bias, running_mean, running_var,
@@ -223,11 +230,15 @@ def _bn_relu_autograd():
             ctx.relu = relu
             ctx.wdtype = weight.dtype
             ctx.legacy_reduce = bn_reduce_legacy()
+            ctx.masked = bool(training and relu and res is not None
+                              and bn_mask_enabled())
             if training:
-                y, mean, invstd = ext.bn_relu_fwd_train(
+                out = ext.bn_relu_fwd_train(
                     x, w32, b32, running_mean, running_var, momentum, eps,
-                    res, relu, ctx.legacy_reduce)
-                ctx.save_for_backward(x, y, w32, b32, mean, invstd)
+                    res, relu, ctx.legacy_reduce, ctx.masked)
+                y, mean, invstd = out[0], out[1], out[2]
+                ctx.save_for_backward(x, out[3] if ctx.masked else y, w32,
+                                      b32, mean, invstd)
             else:
                 y = ext.bn_relu_fwd_eval(x, w32, b32, running_mean.float(),
                                          running_var.float(), eps, res, relu)
@@ -243,9 +254,11 @@ def _bn_relu_autograd():
                 dy, dy2 = dy2, None
             if dy is None:  # no gradient reached either output
                 return (None,) * 11
-            out = ext.bn_relu_bwd(x, y, dy, w32, b32, mean, invstd,
-                                  ctx.with_res, ctx.relu, dy2,
-                                  ctx.legacy_reduce)
+            # y is the ReLU mask (uint8) when ctx.masked
+            out = ext.bn_relu_bwd(x, None if ctx.masked else y, dy, w32,
+                                  b32, mean, invstd, ctx.with_res, ctx.relu,
+                                  dy2, ctx.legacy_reduce,
+                                  y if ctx.masked else None)
             dx, dscale, dbias = out[0], out[1], out[2]
             dres = out[3] if ctx.with_res else None
             return (dx, dres, dscale.to(ctx.wdtype), dbias.to(ctx.wdtype),
@@ -272,6 +285,14 @@ def bn_reduce_legacy() -> bool:
     Same results bit for bit; A/B runs and the oracle of
     tests/test_bn_reduce_gpu.py."""
     return os.environ.get("KUBESHARE_BN_REDUCE", "") == "legacy"
+
+
+def bn_mask_enabled() -> bool:
+    """KUBESHARE_BN_MASK=0 makes the residual BNs (BNReLUFn with res,
+    BNJoinFn) save y for their backward instead of the one-byte-per-8-
+    channels ReLU mask. Same results bit for bit; A/B runs and the
+    oracle of tests/test_bn_mask_gpu.py."""
+    return os.environ.get("KUBESHARE_BN_MASK", "1") != "0"
 
 
 def bn_relu(x, bn, res=None, relu=True, fork=False):
@@ -306,6 +327,106 @@ def bn_relu(x, bn, res=None, relu=True, fork=False):
     return fn.apply(x, res, bn.weight, bn.bias, bn.running_mean,
                     bn.running_var, bn.training, bn.momentum, bn.eps, relu,
                     fork)
+
+
+# ------------------------- downsample BN fused into the residual join
+_BNJoinFn = None
+
+
+def bn_join_enabled() -> bool:
+    """KUBESHARE_BN_JOIN=0 runs a downsample block's join as the two ops
+    bn_relu(x, bn, res=bn_relu(x_d, bn_d, relu=False)) wherever bn_join
+    would have fused them (A/B runs, operator escape hatch)."""
+    return os.environ.get("KUBESHARE_BN_JOIN", "1") != "0"
+
+
+def _bn_join_autograd():
+    """Lazily build the autograd.Function (torch import deferred)."""
+    global _BNJoinFn
+    if _BNJoinFn is not None:
+        return _BNJoinFn
+    import torch
+
+    class BNJoinFn(torch.autograd.Function):
+        """y = relu(bn(x) + bn_d(x_d)) on NHWC bf16, training mode, via
+        hip/bn_join.hip: the downsample BN's output is never allocated
+        and the backward runs one stats and one apply kernel for both
+        BNs. Values and gradients are those of BNReLUFn(x, res=
+        BNReLUFn(x_d, relu=False)), bit for bit; the bias gradient of
+        the two BNs is one sum. fork and the saved ReLU mask are
+        BNReLUFn's."""
+
+        @staticmethod
+        def forward(ctx, x, x_d, weight, bias, running_mean, running_var,
+                    momentum, eps, weight_d, bias_d, running_mean_d,
+                    running_var_d, momentum_d, eps_d, fork):
+            ext = _load()
+            w32, b32 = weight.float(), bias.float()
+            wd32, bd32 = weight_d.float(), bias_d.float()
+            ctx.set_materialize_grads(False)
+            ctx.wdtype = weight.dtype
+            ctx.wdtype_d = weight_d.dtype
+            ctx.legacy_reduce = bn_reduce_legacy()
+            ctx.masked = bn_mask_enabled()
+            out = ext.bn_join_fwd_train(
+                x, w32, b32, running_mean, running_var, momentum, eps,
+                x_d, wd32, bd32, running_mean_d, running_var_d, momentum_d,
+                eps_d, ctx.masked, ctx.legacy_reduce)
+            y = out[0]
+            ctx.save_for_backward(x, x_d, out[5] if ctx.masked else y, w32,
+                                  wd32, *out[1:5])
+            return (y, y.view_as(y)) if fork else y
+
+        @staticmethod
+        def backward(ctx, dy, dy2=None):
+            x, x_d, ym, w32, wd32, mean, invstd, mean_d, invstd_d = \
+                ctx.saved_tensors
+            if dy is None:
+                dy, dy2 = dy2, None
+            if dy is None:  # no gradient reached either output
+                return (None,) * 15
+            dx, dx_d, dscale, dbias, dscale_d = _load().bn_join_bwd(
+                x, x_d, ym, dy, dy2, w32, wd32, mean, invstd, mean_d,
+                invstd_d, ctx.masked, ctx.legacy_reduce)
+            # one sum, two parameters: each gets a tensor of its own
+            return (dx, dx_d, dscale.to(ctx.wdtype), dbias.to(ctx.wdtype),
+                    None, None, None, None, dscale_d.to(ctx.wdtype_d),
+                    dbias.clone().to(ctx.wdtype_d), None, None, None, None,
+                    None)
+
+    _BNJoinFn = BNJoinFn
+    return BNJoinFn
+
+
+def bn_join_supported(x, x_d) -> bool:
+    """True when hip/bn_join.hip covers the pair: both channels-last bf16
+    on the GPU, of one shape, C % 8 == 0 and C <= 2048."""
+    import torch
+
+    return (x.dim() == 4 and x.shape == x_d.shape
+            and x.size(1) % 8 == 0 and x.size(1) <= 2048
+            and all(t.is_cuda and t.dtype == torch.bfloat16
+                    and t.is_contiguous(memory_format=torch.channels_last)
+                    for t in (x, x_d)))
+
+
+def bn_join(x, bn, x_d, bn_d, fork=False):
+    """relu(bn(x) + bn_d(x_d)): the residual join of a downsample block
+    (x the block's last conv output, x_d the downsample conv's) as one
+    fused op (hip/bn_join.hip), using the two nn.BatchNorm2d's
+    parameters and buffers exactly as bn_relu does. Outside
+    bn_join_supported, unless both BNs are in training mode, and under
+    KUBESHARE_BN_JOIN=0 it runs the composition
+    bn_relu(x, bn, res=bn_relu(x_d, bn_d, relu=False), fork=fork), which
+    has its own eager fall-backs. fork is bn_relu's."""
+    if not (bn_join_enabled() and bn.training and bn_d.training
+            and bn_join_supported(x, x_d)):
+        return bn_relu(x, bn, res=bn_relu(x_d, bn_d, relu=False), fork=fork)
+    fn = _BNJoinFn or _bn_join_autograd()
+    return fn.apply(x, x_d, bn.weight, bn.bias, bn.running_mean,
+                    bn.running_var, bn.momentum, bn.eps, bn_d.weight,
+                    bn_d.bias, bn_d.running_mean, bn_d.running_var,
+                    bn_d.momentum, bn_d.eps, fork)
 
 
 # ------------------------------------------- multi-tensor weight casts

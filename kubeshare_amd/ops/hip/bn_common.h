@@ -1,7 +1,7 @@
-// Shared between bn_relu.hip and bn_pool.hip: the bf16 helpers, the
-// pinned per-element expressions, the launch geometry and the host
-// steps both translation units run (the kernels themselves live in
-// bn_relu.hip).
+// Shared between bn_relu.hip, bn_pool.hip and bn_join.hip: the bf16
+// helpers, the pinned per-element expressions, the launch geometry and
+// the host steps these translation units run (the kernels themselves
+// live in bn_relu.hip).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <torch/extension.h>
@@ -68,6 +68,38 @@ __device__ __forceinline__ float bn_acc_dscale(float acc, float g, float xhat,
                              : fmaf(g, xhat, acc);
 }
 
+// Sum of the two gradients of a forked residual join, rounded to bf16
+// as a separate bf16 add kernel would have stored it.
+__device__ __forceinline__ float bn_join_grad(unsigned short a,
+                                              unsigned short b) {
+  return bf16_to_f32(f32_to_bf16(bf16_to_f32(a) + bf16_to_f32(b)));
+}
+
+// xhat = (x - mean) * invstd: a subtraction, then a product
+__device__ __forceinline__ float bn_pool_xhat(float xf, float mu, float is) {
+#pragma clang fp contract(off)
+  return (xf - mu) * is;
+}
+
+// dx = w' * (g - dbias/M - xhat * dscale/M), pinned: one subtraction,
+// one FMA, one product
+__device__ __forceinline__ float bn_pool_dx(float w, float g, float db,
+                                            float xhat, float ds) {
+#pragma clang fp contract(off)
+  const float t = g - db;
+  return w * fmaf(-xhat, ds, t);
+}
+
+// ReLU mask of one lane's 8 stored bf16 values: bit j is set iff value j
+// is > 0, the predicate the backward applies to y (a NaN gives 0).
+__device__ __forceinline__ unsigned char bn_mask_byte(const ushort8& o) {
+  unsigned int m = 0;
+#pragma unroll
+  for (int j = 0; j < 8; j++)
+    m |= (bf16_to_f32(o[j]) > 0.f ? 1u : 0u) << j;
+  return (unsigned char)m;
+}
+
 // ------------------------------------------------------------------ host
 struct BnGeom {
   long long M;  // rows (N*H*W)
@@ -78,6 +110,11 @@ struct BnGeom {
 // sizes the grid-stride launches: `blocks` for the apply kernels,
 // `stat_blocks` for the kernels that leave block partials.
 BnGeom bn_geom_of(const torch::Tensor& x);
+
+// Checks the byte mask of bn_mask_byte against x: contiguous uint8 of
+// shape (N, H, W, C/8) on the GPU.
+void bn_check_mask(const torch::Tensor& mask, const torch::Tensor& x,
+                   const BnGeom& g);
 
 // Forward statistics of a training step: bn_stats_kernel, then
 // bn_reduce_tile_kernel<.., true> (legacy_reduce: the earlier reduce and

@@ -229,19 +229,8 @@ __device__ __forceinline__ bool bn_pool_relu_on(float xf, float sc,
   return f32_to_bf16(f > 0.f ? f : 0.f) != 0;
 }
 
-__device__ __forceinline__ float bn_pool_xhat(float xf, float mu, float is) {
-#pragma clang fp contract(off)
-  return (xf - mu) * is;
-}
-
-// dx = w' * (g - dbias/M - xhat * dscale/M), pinned: one subtraction,
-// one FMA, one product
-__device__ __forceinline__ float bn_pool_dx(float w, float g, float db,
-                                            float xhat, float ds) {
-#pragma clang fp contract(off)
-  const float t = g - db;
-  return w * fmaf(-xhat, ds, t);
-}
+// (bn_pool_xhat and bn_pool_dx, shared with bn_join.hip, are in
+// bn_common.h)
 
 // folded scale' = w*invstd and bias' = b - mean*scale' as
 // bn_finalize_channel computes them (rounded product, then one FMA)

@@ -321,10 +321,14 @@ __global__ void bn_finalize_kernel(const float* __restrict__ sum,
 // y = [relu](x*scale' + bias' [+ res]); scale/bias in registers.
 // RELU=false serves the reference ResNet's downsample-path BNs (no
 // activation), which otherwise fall back to MIOpen's fp32 spatial BN.
-template <bool WITH_RES, bool RELU = true>
+// MASK: also leaves the ReLU mask of each lane's 8 stored values as one
+// byte per lane and row (bn_mask_byte), for the backward to read instead
+// of y.
+template <bool WITH_RES, bool RELU = true, bool MASK = false>
 __global__ void bn_apply_relu_kernel(const ushort8* __restrict__ x,
                                      const ushort8* __restrict__ res,
                                      ushort8* __restrict__ y,
+                                     unsigned char* __restrict__ mask,
                                      const float* __restrict__ scale,
                                      const float* __restrict__ biasf,
                                      long long M, int CG) {
@@ -360,6 +364,7 @@ __global__ void bn_apply_relu_kernel(const ushort8* __restrict__ x,
         o[u][j] = RELU ? bn_relu_bf16(f) : f32_to_bf16(f);
       }
       y[k[u]] = o[u];
+      if (MASK) mask[k[u]] = bn_mask_byte(o[u]);
     }
   }
   for (; row < M; row += stride) {
@@ -375,6 +380,7 @@ __global__ void bn_apply_relu_kernel(const ushort8* __restrict__ x,
       o[j] = RELU ? bn_relu_bf16(f) : f32_to_bf16(f);
     }
     y[k] = o;
+    if (MASK) mask[k] = bn_mask_byte(o);
   }
 }
 
@@ -385,15 +391,15 @@ __global__ void bn_apply_relu_kernel(const ushort8* __restrict__ x,
 // branch) and their gradients arrive separately; the join sum
 // bf16(f32(dy) + f32(dy2)) is formed in registers — bit-for-bit what a
 // separate bf16 add kernel would have written and this kernel re-read.
-__device__ __forceinline__ float bn_join_grad(unsigned short a,
-                                              unsigned short b) {
-  return bf16_to_f32(f32_to_bf16(bf16_to_f32(a) + bf16_to_f32(b)));
-}
-
-// (the pinned dscale accumulation, bn_acc_dscale, is in bn_common.h)
-template <bool WRITE_DYM, bool WITH_DY2 = false>
+// MASK: the predicate y > 0 comes from the byte the forward apply left
+// per lane and row (bn_mask_byte) instead of from y itself: 1/16 of a
+// pass instead of a whole one, the same bits out.
+// (bn_join_grad and the pinned dscale accumulation, bn_acc_dscale, are
+// in bn_common.h)
+template <bool WRITE_DYM, bool WITH_DY2 = false, bool MASK = false>
 __global__ void bn_bwd_stats_kernel(const ushort8* __restrict__ x,
                                     const ushort8* __restrict__ y,
+                                    const unsigned char* __restrict__ mask,
                                     const ushort8* __restrict__ dy,
                                     const ushort8* __restrict__ dy2,
                                     ushort8* __restrict__ dym_out,
@@ -420,7 +426,9 @@ __global__ void bn_bwd_stats_kernel(const ushort8* __restrict__ x,
   // a time. The two-gradient variant reads four tensors per row instead
   // of three, and at U = KS_BN_UNROLL it spills (112 B/lane of scratch
   // under the 128-VGPR budget); two rows at a time it does not.
-  constexpr int U = WITH_DY2 ? KS_BN_UNROLL_DY2 : KS_BN_UNROLL;
+  // (MASK, one gradient: 76 B/lane of scratch at U = KS_BN_UNROLL, none
+  // at two rows; the one-gradient y-reading variant is left as it was)
+  constexpr int U = (WITH_DY2 || MASK) ? KS_BN_UNROLL_DY2 : KS_BN_UNROLL;
   static_assert(KS_BN_UNROLL % U == 0, "sub-batches must tile a group");
   long long row = active ? (long long)blockIdx.x * rows_per_blk + roff : M;
   for (; row + (KS_BN_UNROLL - 1) * stride < M;
@@ -431,12 +439,13 @@ __global__ void bn_bwd_stats_kernel(const ushort8* __restrict__ x,
     for (int h = 0; h < KS_BN_UNROLL; h += U) {
       ushort8 xv[U], yv[U], gv[U];
       ushort8 g2[U];
+      unsigned char mv[U];
       long long k[U];
 #pragma unroll
       for (int u = 0; u < U; u++) {
         k[u] = (row + (h + u) * stride) * CG + cg;
         xv[u] = x[k[u]];
-        yv[u] = y[k[u]];
+        if (MASK) mv[u] = mask[k[u]]; else yv[u] = y[k[u]];
         gv[u] = dy[k[u]];
         if (WITH_DY2) g2[u] = dy2[k[u]];
       }
@@ -447,7 +456,9 @@ __global__ void bn_bwd_stats_kernel(const ushort8* __restrict__ x,
         for (int j = 0; j < 8; j++) {
           float gin = WITH_DY2 ? bn_join_grad(gv[u][j], g2[u][j])
                                : bf16_to_f32(gv[u][j]);
-          float g = bf16_to_f32(yv[u][j]) > 0.f ? gin : 0.f;
+          const bool on = MASK ? ((mv[u] >> j) & 1) != 0
+                               : bf16_to_f32(yv[u][j]) > 0.f;
+          float g = on ? gin : 0.f;
           float xhat = (bf16_to_f32(xv[u][j]) - mu[j]) * is[j];
           adb[j] += g;
           ads[j] = bn_acc_dscale<true>(ads[j], g, xhat, j);
@@ -459,14 +470,18 @@ __global__ void bn_bwd_stats_kernel(const ushort8* __restrict__ x,
   }
   for (; row < M; row += stride) {
     const long long k = row * CG + cg;
-    ushort8 xv = x[k], yv = y[k], gv = dy[k];
+    ushort8 xv = x[k], gv = dy[k];
+    ushort8 yv;
+    unsigned char mv;
+    if (MASK) mv = mask[k]; else yv = y[k];
     ushort8 g2;
     if (WITH_DY2) g2 = dy2[k];
     ushort8 dm;
 #pragma unroll
     for (int j = 0; j < 8; j++) {
       float gin = WITH_DY2 ? bn_join_grad(gv[j], g2[j]) : bf16_to_f32(gv[j]);
-      float g = bf16_to_f32(yv[j]) > 0.f ? gin : 0.f;
+      const bool on = MASK ? ((mv >> j) & 1) != 0 : bf16_to_f32(yv[j]) > 0.f;
+      float g = on ? gin : 0.f;
       float xhat = (bf16_to_f32(xv[j]) - mu[j]) * is[j];
       adb[j] += g;
       ads[j] = bn_acc_dscale<false>(ads[j], g, xhat, j);
@@ -832,6 +847,15 @@ __global__ void bn_fold_eval_kernel(const float* __restrict__ weight,
 }
 
 // ================================================================ host
+void bn_check_mask(const torch::Tensor& mask, const torch::Tensor& x,
+                   const BnGeom& g) {
+  TORCH_CHECK(mask.is_cuda() && mask.scalar_type() == at::kByte &&
+                  mask.is_contiguous() && mask.dim() == 4 &&
+                  mask.size(0) == x.size(0) && mask.size(1) == x.size(2) &&
+                  mask.size(2) == x.size(3) && mask.size(3) == g.CG,
+              "ReLU mask must be a contiguous uint8 (N, H, W, C/8) tensor");
+}
+
 BnGeom bn_geom_of(const torch::Tensor& x) {
   TORCH_CHECK(x.dim() == 4, "bn_relu: 4D NCHW tensor expected");
   TORCH_CHECK(x.scalar_type() == at::kBFloat16, "bn_relu: bf16 only");
@@ -934,11 +958,19 @@ std::vector<torch::Tensor> bn_relu_fwd_train(
     torch::Tensor x, torch::Tensor weight, torch::Tensor bias,
     torch::Tensor running_mean, torch::Tensor running_var, double momentum,
     double eps, c10::optional<torch::Tensor> res, bool relu,
-    bool legacy_reduce) {
+    bool legacy_reduce, bool want_mask) {
   BnGeom g = bn_geom_of(x);
+  TORCH_CHECK(!want_mask || (res.has_value() && relu),
+              "bn_relu_fwd_train: the ReLU mask is for residual BNs with "
+              "ReLU");
   auto stream = at::cuda::getCurrentCUDAStream();
   auto f32 = x.options().dtype(at::kFloat);
   auto y = at::empty_like(x);
+  // one byte per lane and row: (N, H, W, C/8)
+  torch::Tensor mask;
+  if (want_mask)
+    mask = at::empty({x.size(0), x.size(2), x.size(3), (long long)g.CG},
+                     x.options().dtype(at::kByte));
   auto save_mean = at::empty({g.C}, f32);
   auto save_invstd = at::empty({g.C}, f32);
   auto scale = at::empty({g.C}, f32);
@@ -958,15 +990,19 @@ std::vector<torch::Tensor> bn_relu_fwd_train(
                            ? reinterpret_cast<const ushort8*>(res->data_ptr())
                            : nullptr,
                        reinterpret_cast<ushort8*>(y.data_ptr()),
+                       want_mask ? mask.data_ptr<unsigned char>() : nullptr,
                        scale.data_ptr<float>(), biasf.data_ptr<float>(), g.M,
                        g.CG);
   };
-  if (res.has_value())
+  if (want_mask)
+    launch_apply(bn_apply_relu_kernel<true, true, true>);
+  else if (res.has_value())
     relu ? launch_apply(bn_apply_relu_kernel<true, true>)
          : launch_apply(bn_apply_relu_kernel<true, false>);
   else
     relu ? launch_apply(bn_apply_relu_kernel<false, true>)
          : launch_apply(bn_apply_relu_kernel<false, false>);
+  if (want_mask) return {y, save_mean, save_invstd, mask};
   return {y, save_mean, save_invstd};
 }
 
@@ -990,8 +1026,8 @@ torch::Tensor bn_relu_fwd_eval(torch::Tensor x, torch::Tensor weight,
                            ? reinterpret_cast<const ushort8*>(res->data_ptr())
                            : nullptr,
                        reinterpret_cast<ushort8*>(y.data_ptr()),
-                       scale.data_ptr<float>(), biasf.data_ptr<float>(), g.M,
-                       g.CG);
+                       (unsigned char*)nullptr, scale.data_ptr<float>(),
+                       biasf.data_ptr<float>(), g.M, g.CG);
   };
   if (res.has_value())
     relu ? launch_apply(bn_apply_relu_kernel<true, true>)
@@ -1002,19 +1038,28 @@ torch::Tensor bn_relu_fwd_eval(torch::Tensor x, torch::Tensor weight,
   return y;
 }
 
-std::vector<torch::Tensor> bn_relu_bwd(torch::Tensor x, torch::Tensor y,
-                                       torch::Tensor dy, torch::Tensor weight,
-                                       torch::Tensor bias, torch::Tensor mean,
-                                       torch::Tensor invstd, bool need_dres,
-                                       bool relu,
-                                       c10::optional<torch::Tensor> dy2,
-                                       bool legacy_reduce) {
+std::vector<torch::Tensor> bn_relu_bwd(
+    torch::Tensor x, c10::optional<torch::Tensor> y, torch::Tensor dy,
+    torch::Tensor weight, torch::Tensor bias, torch::Tensor mean,
+    torch::Tensor invstd, bool need_dres, bool relu,
+    c10::optional<torch::Tensor> dy2, bool legacy_reduce,
+    c10::optional<torch::Tensor> mask) {
   TORCH_CHECK(relu || !need_dres,
               "bn_relu_bwd: residual path requires the ReLU variant");
   BnGeom g = bn_geom_of(x);
-  TORCH_CHECK(dy.sizes() == x.sizes() && y.sizes() == x.sizes() &&
-                  dy.scalar_type() == at::kBFloat16,
+  TORCH_CHECK(dy.sizes() == x.sizes() && dy.scalar_type() == at::kBFloat16,
               "bn_relu_bwd: dy must be bf16 of x's shape");
+  // residual BNs take the ReLU mask from y, or from the byte mask the
+  // forward left (bn_apply_relu_kernel<.., MASK>) when that is given
+  const bool use_mask = need_dres && mask.has_value() && mask->defined();
+  if (use_mask) {
+    bn_check_mask(*mask, x, g);
+  } else if (need_dres) {
+    TORCH_CHECK(y.has_value() && y->defined() && y->sizes() == x.sizes() &&
+                    y->scalar_type() == at::kBFloat16 &&
+                    y->is_contiguous(at::MemoryFormat::ChannelsLast),
+                "bn_relu_bwd: y must be channels-last bf16 of x's shape");
+  }
   // second upstream gradient (y forked to two consumers): folded into
   // the residual stats kernel when it has dy's layout; anything else is
   // summed here first and takes the existing path
@@ -1052,7 +1097,10 @@ std::vector<torch::Tensor> bn_relu_bwd(torch::Tensor x, torch::Tensor y,
       hipLaunchKernelGGL(kern, dim3(g.stat_blocks), dim3(KS_BN_BLOCK), 0,
                          stream.stream(),
                          reinterpret_cast<const ushort8*>(x.data_ptr()),
-                         reinterpret_cast<const ushort8*>(y.data_ptr()),
+                         use_mask ? nullptr
+                                  : reinterpret_cast<const ushort8*>(
+                                        y->data_ptr()),
+                         use_mask ? mask->data_ptr<unsigned char>() : nullptr,
                          reinterpret_cast<const ushort8*>(dy.data_ptr()),
                          fold_dy2 ? reinterpret_cast<const ushort8*>(
                                         dy2->data_ptr())
@@ -1061,8 +1109,12 @@ std::vector<torch::Tensor> bn_relu_bwd(torch::Tensor x, torch::Tensor y,
                          mean.data_ptr<float>(), invstd.data_ptr<float>(),
                          part.data_ptr<float>(), g.M, g.CG);
     };
-    fold_dy2 ? launch_rstats(bn_bwd_stats_kernel<true, true>)
-             : launch_rstats(bn_bwd_stats_kernel<true, false>);
+    if (use_mask)
+      fold_dy2 ? launch_rstats(bn_bwd_stats_kernel<true, true, true>)
+               : launch_rstats(bn_bwd_stats_kernel<true, false, true>);
+    else
+      fold_dy2 ? launch_rstats(bn_bwd_stats_kernel<true, true>)
+               : launch_rstats(bn_bwd_stats_kernel<true, false>);
     launch_reduce();
     hipLaunchKernelGGL(bn_bwd_apply_dym_kernel, dim3(g.blocks),
                        dim3(KS_BN_BLOCK), 0, stream.stream(),

@@ -18,6 +18,8 @@
 //    max-pool and the multi-tensor f32 <-> bf16 casts (bound below).
 //  - bn_pool.hip: BN+ReLU+max-pool in one op, the full-resolution
 //    activation never written (ResNet stem, VGG pools).
+//  - bn_join.hip: a downsample block's two BNs, the residual add and the
+//    ReLU in one op; the downsample BN's output is never written.
 //  - bias_relu.hip: bias+ReLU(+max-pool) for conv layers without a BN
 //    (the plain VGG16), bias gradient in the same backward pass.
 #include <hip/hip_runtime.h>
@@ -318,18 +320,32 @@ std::vector<torch::Tensor> bn_relu_fwd_train(
     torch::Tensor x, torch::Tensor weight, torch::Tensor bias,
     torch::Tensor running_mean, torch::Tensor running_var, double momentum,
     double eps, c10::optional<torch::Tensor> res, bool relu,
-    bool legacy_reduce);
+    bool legacy_reduce, bool want_mask);
 torch::Tensor bn_relu_fwd_eval(torch::Tensor x, torch::Tensor weight,
                                torch::Tensor bias, torch::Tensor rmean,
                                torch::Tensor rvar, double eps,
                                c10::optional<torch::Tensor> res, bool relu);
-std::vector<torch::Tensor> bn_relu_bwd(torch::Tensor x, torch::Tensor y,
-                                       torch::Tensor dy, torch::Tensor weight,
-                                       torch::Tensor bias, torch::Tensor mean,
-                                       torch::Tensor invstd, bool need_dres,
-                                       bool relu,
-                                       c10::optional<torch::Tensor> dy2,
-                                       bool legacy_reduce);
+std::vector<torch::Tensor> bn_relu_bwd(
+    torch::Tensor x, c10::optional<torch::Tensor> y, torch::Tensor dy,
+    torch::Tensor weight, torch::Tensor bias, torch::Tensor mean,
+    torch::Tensor invstd, bool need_dres, bool relu,
+    c10::optional<torch::Tensor> dy2, bool legacy_reduce,
+    c10::optional<torch::Tensor> mask);
+
+// downsample BN fused into the residual join (bn_join.hip)
+std::vector<torch::Tensor> bn_join_fwd_train(
+    torch::Tensor x, torch::Tensor weight, torch::Tensor bias,
+    torch::Tensor running_mean, torch::Tensor running_var, double momentum,
+    double eps, torch::Tensor x_d, torch::Tensor weight_d,
+    torch::Tensor bias_d, torch::Tensor running_mean_d,
+    torch::Tensor running_var_d, double momentum_d, double eps_d,
+    bool want_mask, bool legacy_reduce);
+std::vector<torch::Tensor> bn_join_bwd(
+    torch::Tensor x, torch::Tensor x_d, torch::Tensor y_or_mask,
+    torch::Tensor dy, c10::optional<torch::Tensor> dy2, torch::Tensor weight,
+    torch::Tensor weight_d, torch::Tensor mean, torch::Tensor invstd,
+    torch::Tensor mean_d, torch::Tensor invstd_d, bool use_mask,
+    bool legacy_reduce);
 
 // multi-tensor f32 <-> bf16 casts (cast.hip)
 std::vector<c10::optional<torch::Tensor>> cast_f32_to_bf16_multi(
@@ -384,12 +400,33 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("bn_relu_fwd_train", &bn_relu_fwd_train, py::arg("x"),
         py::arg("weight"), py::arg("bias"), py::arg("running_mean"),
         py::arg("running_var"), py::arg("momentum"), py::arg("eps"),
-        py::arg("res"), py::arg("relu"), py::arg("legacy_reduce") = false);
+        py::arg("res"), py::arg("relu"), py::arg("legacy_reduce") = false,
+        py::arg("want_mask") = false,
+        "{y, mean, invstd} and, with want_mask (res and relu only), the "
+        "uint8 (N, H, W, C/8) ReLU mask");
   m.def("bn_relu_fwd_eval", &bn_relu_fwd_eval);
   m.def("bn_relu_bwd", &bn_relu_bwd, py::arg("x"), py::arg("y"),
         py::arg("dy"), py::arg("weight"), py::arg("bias"), py::arg("mean"),
         py::arg("invstd"), py::arg("need_dres"), py::arg("relu"),
-        py::arg("dy2") = py::none(), py::arg("legacy_reduce") = false);
+        py::arg("dy2") = py::none(), py::arg("legacy_reduce") = false,
+        py::arg("mask") = py::none(),
+        "{dx, dscale, dbias[, dres]}; with mask (residual BNs) y may be "
+        "None");
+  m.def("bn_join_fwd_train", &bn_join_fwd_train, py::arg("x"),
+        py::arg("weight"), py::arg("bias"), py::arg("running_mean"),
+        py::arg("running_var"), py::arg("momentum"), py::arg("eps"),
+        py::arg("x_d"), py::arg("weight_d"), py::arg("bias_d"),
+        py::arg("running_mean_d"), py::arg("running_var_d"),
+        py::arg("momentum_d"), py::arg("eps_d"), py::arg("want_mask"),
+        py::arg("legacy_reduce") = false,
+        "relu(bn(x) + bn_d(x_d)): {y, mean, invstd, mean_d, invstd_d} and, "
+        "with want_mask, the uint8 (N, H, W, C/8) ReLU mask");
+  m.def("bn_join_bwd", &bn_join_bwd, py::arg("x"), py::arg("x_d"),
+        py::arg("y_or_mask"), py::arg("dy"), py::arg("dy2"),
+        py::arg("weight"), py::arg("weight_d"), py::arg("mean"),
+        py::arg("invstd"), py::arg("mean_d"), py::arg("invstd_d"),
+        py::arg("use_mask"), py::arg("legacy_reduce") = false,
+        "{dx, dx_d, dscale, dbias, dscale_d}; dbias serves both BNs");
   m.def("cast_f32_to_bf16_multi", &cast_f32_to_bf16_multi,
         "f32 -> bf16 (torch rounding) of every tensor of a list in as few "
         "launches as the kernel-argument limit allows; None stays None");
