@@ -17,7 +17,8 @@ _SRCS = [os.path.join(_HERE, "hip", "ks_ops.hip"),
          os.path.join(_HERE, "hip", "bn_pool.hip"),
          os.path.join(_HERE, "hip", "bn_join.hip"),
          os.path.join(_HERE, "hip", "bias_relu.hip"),
-         os.path.join(_HERE, "hip", "cast.hip")]
+         os.path.join(_HERE, "hip", "cast.hip"),
+         os.path.join(_HERE, "hip", "conv_split.hip")]
 
 _ext = None
 
@@ -165,6 +166,10 @@ class FusedSGD:
     def step(self):
         # torch SGD's first step sets v = g + wd*p (no mu*v term since v
         # starts at 0) — identical here because v == 0.
+        # (a backward that ended early or raised never reached
+        # CastWeightsFn's join: no side-stream weight gradient outlives
+        # the step)
+        wgrad_join()
         if self._step_graph is not None and \
                 self._graph_ptrs == self._ptrs():
             self._step_graph.replay()
@@ -445,6 +450,9 @@ def _cast_weights_autograd():
         of hip/cast.hip per 128 tensors, strides preserved; the backward
         casts the incoming bf16 gradients back to f32 the same way. A
         gradient that is already f32, or None, passes through untouched.
+        The backward first joins the weight-gradient side stream
+        (wgrad_join): autograd runs this node once every staged weight's
+        gradient has been issued, and it is their first reader.
         Values are exactly those of w.to(torch.bfloat16) and g.float():
         this replaces autocast's per-weight cast launches and their
         ToCopyBackward0 nodes, nothing else."""
@@ -456,6 +464,7 @@ def _cast_weights_autograd():
 
         @staticmethod
         def backward(ctx, *grads):
+            wgrad_join()
             out = list(grads)
             idx = [i for i, g in enumerate(grads)
                    if g is not None and g.dtype == torch.bfloat16]
@@ -501,6 +510,7 @@ def stage_lowp_weights(convs):
     weights = [m.weight for m in convs]
     if not all(w.is_cuda and w.dtype == torch.float32 for w in weights):
         return []
+    wgrad_join()  # nothing of an abandoned backward runs into this step
     for m, w in zip(convs, cast_weights_bf16(weights)):
         m._lowp_weight = w
     return convs
@@ -510,6 +520,46 @@ def clear_lowp_weights(convs):
     """Drop the staged copies (the autograd graph keeps what it needs)."""
     for m in convs:
         m._lowp_weight = None
+
+
+# ------------------------------ conv weight gradients on a side stream
+def wrw_stream_enabled() -> bool:
+    """KUBESHARE_WRW_STREAM=0 keeps every models.conv.LowpConv2d on the
+    stock convolution, whose backward runs the data gradient and the
+    weight gradient back to back on one stream, instead of
+    conv2d_split (A/B runs, operator escape hatch).
+    KUBESHARE_WRW_PRIORITY=<int> (read once, when the side stream is
+    taken) asks PyTorch's stream pool for that priority: 0, the default,
+    is also the lowest the pool offers on HIP, -1 the high-priority
+    pool."""
+    return os.environ.get("KUBESHARE_WRW_STREAM", "1") != "0"
+
+
+def conv2d_split(x, w, stride=(1, 1), padding=(0, 0), dilation=(1, 1),
+                 groups=1):
+    """Bias-free F.conv2d(x, w, None, stride, padding, dilation, groups)
+    for CUDA tensors through hip/conv_split.hip: same ATen entry, same
+    MIOpen kernels, same values, but the backward issues the weight
+    gradient on a side stream (one per device), where MIOpen's zero-fill
+    and cast kernels around each split-K weight-gradient kernel run
+    beside the main stream's kernels instead of between them. The
+    returned dW is NOT ordered with the stream that called backward()
+    until wgrad_join() has run on that stream: CastWeightsFn.backward,
+    FusedSGD.step and stage_lowp_weights call it, and any other reader
+    must. Inside a graph capture the backward does not fork. Double
+    backward raises."""
+    def two(v):
+        return [int(v), int(v)] if isinstance(v, int) else [int(i) for i in v]
+    return _load().conv2d_split(x, w, two(stride), two(padding),
+                                two(dilation), int(groups))
+
+
+def wgrad_join():
+    """The current stream waits for every weight gradient conv2d_split
+    has issued on the side stream; a no-op with nothing pending (and
+    without the extension loaded, when nothing can be)."""
+    if _ext is not None:
+        _ext.wgrad_join()
 
 
 # ------------------------------------------------------ fused max-pool

@@ -388,6 +388,15 @@ std::vector<torch::Tensor> bias_relu_pool_bwd(
     torch::Tensor dy, torch::Tensor idx, torch::Tensor y,
     std::vector<int64_t> input_sizes, int64_t k, int64_t s, int64_t p);
 
+// convolution whose backward runs the weight gradient on a side stream
+// (conv_split.hip)
+torch::Tensor conv2d_split(torch::Tensor x, torch::Tensor w,
+                           std::vector<int64_t> stride,
+                           std::vector<int64_t> padding,
+                           std::vector<int64_t> dilation, int64_t groups);
+void wgrad_join();
+bool wgrad_pending();
+
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("burn", &burn, "occupy the GPU for ~ms milliseconds",
         py::arg("ms"), py::arg("blocks") = 1024, py::arg("threads") = 256);
@@ -457,4 +466,14 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("bias_relu_pool_bwd", &bias_relu_pool_bwd, py::arg("dy"),
         py::arg("idx"), py::arg("y"), py::arg("input_sizes"), py::arg("k"),
         py::arg("s"), py::arg("p"), "{dx, db}");
+  m.def("conv2d_split", &conv2d_split, py::arg("x"), py::arg("w"),
+        py::arg("stride"), py::arg("padding"), py::arg("dilation"),
+        py::arg("groups"),
+        "bias-free at::convolution; its backward runs the weight gradient "
+        "on a side stream (join with wgrad_join)");
+  m.def("wgrad_join", &wgrad_join,
+        "the current stream waits for every pending side-stream weight "
+        "gradient; a no-op with nothing pending");
+  m.def("wgrad_pending", &wgrad_pending,
+        "True while a side-stream weight gradient has not been joined");
 }
