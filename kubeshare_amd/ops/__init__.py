@@ -18,7 +18,8 @@ _SRCS = [os.path.join(_HERE, "hip", "ks_ops.hip"),
          os.path.join(_HERE, "hip", "bn_join.hip"),
          os.path.join(_HERE, "hip", "bias_relu.hip"),
          os.path.join(_HERE, "hip", "cast.hip"),
-         os.path.join(_HERE, "hip", "conv_split.hip")]
+         os.path.join(_HERE, "hip", "conv_split.hip"),
+         os.path.join(_HERE, "hip", "grad_bucket.hip")]
 
 _ext = None
 
@@ -92,13 +93,42 @@ class FusedSGD:
 
     KUBESHARE_SGD_MULTI=0 selects the per-tensor kernel (one launch per
     tensor) for A/B runs; KUBESHARE_SGD_GRAPH=0 disables the capture.
+
+    process_group (a torch.distributed group, or True for the default
+    group) makes the optimizer average the gradients over that group,
+    for a model that is NOT wrapped in DistributedDataParallel. step()
+    is then: wgrad_join(); pack every gradient, scaled by 1/world, into
+    one persistent flat GradBucket of grad_dtype (f32 or bf16); ONE
+    all-reduce of the bucket; the multi-tensor SGD with the bucket's
+    views as gradients (a bf16 bucket is upcast in registers). These
+    steps launch eagerly, never from a captured graph (a gloo collective
+    cannot be captured), and always through the multi-tensor kernel.
+    Unlike the ungrouped step, which skips a parameter whose gradient is
+    None, the grouped step gives such a parameter a zero gradient and
+    updates it like any other (momentum and weight decay still move it):
+    every rank must all-reduce the same layout, and a rank that raised
+    or skipped would leave its peers waiting. With process_group=None
+    nothing of this exists and the optimizer is the ungrouped one.
     """
 
     def __init__(self, params, lr: float, momentum: float = 0.9,
-                 weight_decay: float = 0.0, graph_mode: str = "auto"):
+                 weight_decay: float = 0.0, graph_mode: str = "auto",
+                 process_group=None, grad_dtype=None):
         import torch
 
         self.params = [p for p in params if p.requires_grad]
+        self._bucket = None
+        if process_group is not None and process_group is not False:
+            import torch.distributed as dist
+
+            self._group = None if process_group is True else process_group
+            self._world = dist.get_world_size(self._group)
+            self._bucket = GradBucket(
+                self.params,
+                torch.float32 if grad_dtype is None else grad_dtype)
+        elif grad_dtype not in (None, torch.float32):
+            raise ValueError("grad_dtype needs a process_group: ungrouped "
+                             "steps read the f32 gradients themselves")
         self.lr = lr
         self.momentum = momentum
         self.weight_decay = weight_decay
@@ -152,6 +182,19 @@ class FusedSGD:
         ext.sgd_momentum_(ps, gs, vs, self.lr, self.momentum,
                           self.weight_decay)
 
+    def _group_step(self):
+        """Average over the group, then update from the bucket (see the
+        class docstring); the side stream has been joined."""
+        import torch
+        bucket = self._bucket
+        bucket.pack([p.grad for p in self.params], 1.0 / self._world)
+        bucket.all_reduce(self._group)
+        ext = _load()
+        sgd = ext.sgd_momentum_multi_ if bucket.dtype == torch.float32 \
+            else ext.sgd_momentum_multi_bf16g_
+        sgd([p.data for p in self.params], bucket.views, self.momenta,
+            self.lr, self.momentum, self.weight_decay)
+
     def _capture(self):
         import torch
         ptrs = self._ptrs()
@@ -170,6 +213,9 @@ class FusedSGD:
         # CastWeightsFn's join: no side-stream weight gradient outlives
         # the step)
         wgrad_join()
+        if self._bucket is not None:
+            self._group_step()
+            return
         if self._step_graph is not None and \
                 self._graph_ptrs == self._ptrs():
             self._step_graph.replay()
@@ -183,6 +229,153 @@ class FusedSGD:
                 self._capture()
             except Exception:  # noqa: BLE001 — capture is an optimization
                 self._graph_mode = "off"
+
+
+# ------------------------------------------------- flat gradient bucket
+def _dense(t) -> bool:
+    """Non-overlapping and dense: t's elements fill numel() consecutive
+    storage slots in some dimension order (contiguous, channels-last,
+    any permutation of a contiguous tensor)."""
+    expect = 1
+    for size, stride in sorted(
+            ((s, st) for s, st in zip(t.size(), t.stride()) if s != 1),
+            key=lambda d: d[1]):
+        if size == 0:
+            return True
+        if stride != expect:
+            return False
+        expect *= size
+    return True
+
+
+class GradBucket:
+    """One persistent flat buffer with a segment per tensor of `params`
+    (f32 tensors on one device), of dtype f32 or bf16: what a gang rank
+    all-reduces in ONE collective (FusedSGD(process_group=...)) or
+    broadcasts (broadcast_parameters).
+
+    Segment t starts at offsets[t], a multiple of 8 elements (16 bytes
+    in bf16, 32 in f32, so every segment takes the kernels' 16-byte
+    vector path), and holds the tensor's flat dense storage in storage
+    order; the padding between segments is zeroed here and never written
+    again. views[t] = flat.as_strided(p.size(), p.stride(), offsets[t]):
+    the segment seen with the parameter's sizes and strides, which is
+    what the multi-tensor SGD takes as a gradient. Parameters must be
+    non-overlapping and dense (ValueError otherwise).
+
+    pack(tensors, scale) writes view_t = (tensor_t * f32(scale)).to(dtype)
+    and zeros for a None entry; unpack(tensors) writes tensor_t =
+    view_t.float(). On CUDA both run hip/grad_bucket.hip (up to 128
+    tensors per launch) and nothing else: no eager fall-back. On CPU
+    tensors they run exactly those torch expressions, so the layout
+    logic is testable without a GPU."""
+
+    ALIGN = 8  # elements
+
+    def __init__(self, params, dtype=None):
+        import torch
+
+        self.params = list(params)
+        self.dtype = torch.float32 if dtype is None else dtype
+        if self.dtype not in (torch.float32, torch.bfloat16):
+            raise ValueError("GradBucket: dtype must be float32 or "
+                             f"bfloat16, not {self.dtype}")
+        device = self.params[0].device if self.params else "cpu"
+        self.offsets = []
+        end = 0
+        for p in self.params:
+            if p.dtype != torch.float32 or p.device != device:
+                raise ValueError("GradBucket: f32 tensors on one device "
+                                 "expected")
+            if not _dense(p):
+                raise ValueError(
+                    "GradBucket: parameters must be non-overlapping and "
+                    f"dense, got sizes {tuple(p.size())} strides "
+                    f"{tuple(p.stride())}")
+            self.offsets.append(end)
+            end += p.numel()
+            end += -end % self.ALIGN
+        self.flat = torch.zeros(end, dtype=self.dtype, device=device)
+        self.views = [self.flat.as_strided(p.size(), p.stride(), off)
+                      for p, off in zip(self.params, self.offsets)]
+
+    def _check(self, tensors):
+        tensors = list(tensors)
+        if len(tensors) != len(self.views):
+            raise ValueError(f"GradBucket: {len(self.views)} tensors "
+                             f"expected, got {len(tensors)}")
+        return tensors
+
+    def pack(self, tensors, scale: float = 1.0):
+        """view_t = (tensor_t * scale).to(dtype), zeros for None. The
+        scale is rounded to f32 once, here; the product is one f32
+        multiply per element. A tensor whose strides differ from its
+        parameter's (a contiguous gradient for a channels-last weight)
+        is re-strided first."""
+        import torch
+
+        tensors = self._check(tensors)
+        scale = torch.tensor(scale, dtype=torch.float32).item()
+        if self.flat.is_cuda:
+            _load().grad_pack_multi(tensors, self.flat, self.offsets, scale,
+                                    self.views)
+            return
+        with torch.no_grad():
+            for view, g in zip(self.views, tensors):
+                if g is None:
+                    view.zero_()
+                else:
+                    view.copy_((g * scale).to(self.dtype))
+
+    def unpack(self, tensors):
+        """tensor_t = view_t.float(), in place; None entries are
+        skipped. Every tensor must have its parameter's sizes and
+        strides."""
+        import torch
+
+        tensors = self._check(tensors)
+        for view, t in zip(self.views, tensors):
+            if t is not None and (t.size() != view.size()
+                                  or t.stride() != view.stride()):
+                raise ValueError("GradBucket.unpack: destination with the "
+                                 "parameter's sizes and strides expected")
+        if self.flat.is_cuda:
+            _load().grad_unpack_multi(self.flat, self.offsets, tensors)
+            return
+        with torch.no_grad():
+            for view, t in zip(self.views, tensors):
+                if t is not None:
+                    t.copy_(view.float())
+
+    def all_reduce(self, group=None):
+        """Sum the flat buffer over the group (None: the default
+        group), in place; the caller's pack() scale makes it a mean."""
+        import torch.distributed as dist
+
+        dist.all_reduce(self.flat, op=dist.ReduceOp.SUM, group=group)
+
+
+def broadcast_parameters(model, src: int = 0, group=None):
+    """Give every rank of the group rank `src`'s parameters and
+    floating-point buffers (BN running statistics): all of them are
+    packed into a temporary f32 GradBucket, sent by ONE broadcast and
+    unpacked in place. Call it once, before training, on a model that is
+    not wrapped in DistributedDataParallel. `src` is a global rank.
+
+    Nothing synchronises the buffers afterwards: BN running statistics
+    are local to a rank (each follows its own batches), exactly as under
+    DistributedDataParallel(broadcast_buffers=False). Integer buffers
+    (num_batches_tracked) are left alone. Tensors must be f32."""
+    import torch
+    import torch.distributed as dist
+
+    tensors = [p.data for p in model.parameters()]
+    tensors += [b for b in model.buffers() if b.is_floating_point()]
+    with torch.no_grad():
+        bucket = GradBucket(tensors, torch.float32)
+        bucket.pack(tensors)
+        dist.broadcast(bucket.flat, src=src, group=group)
+        bucket.unpack(tensors)
 
 
 # ---------------------------------------------------- fused BN+ReLU(+add)

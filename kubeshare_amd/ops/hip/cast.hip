@@ -22,6 +22,8 @@
 
 #include <vector>
 
+#include "cast_common.h"
+
 #define KS_CAST_THREADS 256
 #define KS_CAST_VPT 4  // 8-element vectors per thread, all loads first
 #define KS_CAST_CHUNK (KS_CAST_THREADS * KS_CAST_VPT * 8)
@@ -39,26 +41,6 @@ struct CastMultiArgs {
 };
 static_assert(sizeof(CastMultiArgs) <= 4096,
               "CastMultiArgs must fit the 4 KiB kernel-argument segment");
-
-__device__ __forceinline__ unsigned short cast_f32_to_bf16(float f) {
-  union {
-    float f;
-    unsigned int i;
-  } v;
-  v.f = f;
-  if ((v.i & 0x7fffffffu) > 0x7f800000u) return 0x7FC0;  // any NaN
-  v.i += 0x7fffu + ((v.i >> 16) & 1);
-  return (unsigned short)(v.i >> 16);
-}
-
-__device__ __forceinline__ float cast_bf16_to_f32(unsigned short u) {
-  union {
-    unsigned int i;
-    float f;
-  } v;
-  v.i = ((unsigned int)u) << 16;
-  return v.f;
-}
 
 // 8 elements: two float4 on the f32 side, one 16-byte vector on the
 // bf16 side

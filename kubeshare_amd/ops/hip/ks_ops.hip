@@ -13,7 +13,10 @@
 //    as the bit-exact reference and for KUBESHARE_SGD_MULTI=0.
 //  - sgd_mom_multi_f32_kernel: the same update for up to 110 tensors per
 //    launch; pointers and block prefix sums ride in the kernel arguments
-//    (ResNet50's 161 tensors: 2 launches instead of 161).
+//    (ResNet50's 161 tensors: 2 launches instead of 161). Templated on
+//    the gradient type: f32, or bf16 from a bf16 gradient bucket.
+//  - grad_bucket.hip: multi-tensor pack / unpack between per-parameter
+//    gradients and the flat bucket a gang all-reduces (bound below).
 //  - bn_relu.hip / pool.hip / cast.hip: fused NHWC bf16 BN+ReLU(+add),
 //    max-pool and the multi-tensor f32 <-> bf16 casts (bound below).
 //  - bn_pool.hip: BN+ReLU+max-pool in one op, the full-resolution
@@ -26,6 +29,7 @@
 #include <torch/extension.h>
 #include <ATen/cuda/CUDAContext.h>
 
+#include <type_traits>
 #include <vector>
 
 #define WAVE 64
@@ -128,9 +132,12 @@ __global__ void sgd_mom_f32_kernel(float* __restrict__ p,
 #define KS_SGD_CHUNK (KS_SGD_THREADS * KS_SGD_VPT * 4)
 #define KS_SGD_MAX_TENSORS 110
 
+// G is the gradient's element type: float, or unsigned short holding
+// bf16 bits (a bf16 ops.GradBucket's views), upcast in registers.
+template <typename G>
 struct SgdMultiArgs {
   float* p[KS_SGD_MAX_TENSORS];
-  const float* g[KS_SGD_MAX_TENSORS];
+  const G* g[KS_SGD_MAX_TENSORS];
   float* v[KS_SGD_MAX_TENSORS];
   long long n[KS_SGD_MAX_TENSORS];
   // blk[t] = first block of tensor t; blk[count] = grid size
@@ -138,11 +145,32 @@ struct SgdMultiArgs {
   int count;
   float lr, mu, wd;
 };
-static_assert(sizeof(SgdMultiArgs) <= 4096,
+static_assert(sizeof(SgdMultiArgs<float>) <= 4096 &&
+                  sizeof(SgdMultiArgs<unsigned short>) <= 4096,
               "SgdMultiArgs must fit the 4 KiB kernel-argument segment");
 
+// four / one gradient element(s) as f32 (bf16 -> f32 is exact)
+__device__ __forceinline__ float4 sgd_load_g4(const float* g, int k) {
+  return reinterpret_cast<const float4*>(g)[k];
+}
+__device__ __forceinline__ float4 sgd_load_g4(const unsigned short* g,
+                                              int k) {
+  const ushort4 u = reinterpret_cast<const ushort4*>(g)[k];
+  return make_float4(__uint_as_float((unsigned int)u.x << 16),
+                     __uint_as_float((unsigned int)u.y << 16),
+                     __uint_as_float((unsigned int)u.z << 16),
+                     __uint_as_float((unsigned int)u.w << 16));
+}
+__device__ __forceinline__ float sgd_load_g(const float* g, int k) {
+  return g[k];
+}
+__device__ __forceinline__ float sgd_load_g(const unsigned short* g, int k) {
+  return __uint_as_float((unsigned int)g[k] << 16);
+}
+
+template <typename G>
 __global__ void __launch_bounds__(KS_SGD_THREADS)
-sgd_mom_multi_f32_kernel(const SgdMultiArgs a) {
+sgd_mom_multi_f32_kernel(const SgdMultiArgs<G> a) {
   const int b = blockIdx.x;
   // largest t with blk[t] <= b (blk is non-decreasing, blk[0] == 0,
   // b < blk[count]; tensors own >= 1 block, so the answer is unique)
@@ -152,7 +180,7 @@ sgd_mom_multi_f32_kernel(const SgdMultiArgs a) {
     if (a.blk[mid] <= b) lo = mid; else hi = mid - 1;
   }
   float* __restrict__ p = a.p[lo];
-  const float* __restrict__ g = a.g[lo];
+  const G* __restrict__ g = a.g[lo];
   float* __restrict__ v = a.v[lo];
   const long long n = a.n[lo];
   const float lr = a.lr, mu = a.mu, wd = a.wd;
@@ -165,11 +193,12 @@ sgd_mom_multi_f32_kernel(const SgdMultiArgs a) {
   const int tid = threadIdx.x;
   // base is a multiple of 4 elements, so the chunk start is 16-byte
   // aligned exactly when the tensor start is; misaligned views
-  // (narrow() at an odd offset) take the scalar path
-  const bool vec = (((uintptr_t)p | (uintptr_t)g | (uintptr_t)v) & 15) == 0;
+  // (narrow() at an odd offset) take the scalar path. (Four gradient
+  // elements are 16 bytes of f32, 8 of bf16.)
+  const uintptr_t ga = (uintptr_t)g * (sizeof(float) / sizeof(G));
+  const bool vec = (((uintptr_t)p | ga | (uintptr_t)v) & 15) == 0;
   if (vec) {
     const int len4 = len >> 2;
-    const float4* g4 = reinterpret_cast<const float4*>(g);
     float4* p4 = reinterpret_cast<float4*>(p);
     float4* v4 = reinterpret_cast<float4*>(v);
     if (len == KS_SGD_CHUNK) {
@@ -178,7 +207,7 @@ sgd_mom_multi_f32_kernel(const SgdMultiArgs a) {
       for (int u = 0; u < KS_SGD_VPT; u++) {
         const int k = tid + u * KS_SGD_THREADS;
         pv[u] = p4[k];
-        gv[u] = g4[k];
+        gv[u] = sgd_load_g4(g, k);
         vv[u] = v4[k];
       }
 #pragma unroll
@@ -191,14 +220,14 @@ sgd_mom_multi_f32_kernel(const SgdMultiArgs a) {
       return;
     }
     for (int k = tid; k < len4; k += KS_SGD_THREADS) {
-      float4 pv = p4[k], gv = g4[k], vv = v4[k];
+      float4 pv = p4[k], gv = sgd_load_g4(g, k), vv = v4[k];
       sgd_mom_update4(pv, gv, vv, lr, mu, wd);
       v4[k] = vv;
       p4[k] = pv;
     }
     for (int k = len4 * 4 + tid; k < len; k += KS_SGD_THREADS) {
       float pv = p[k], vv = v[k];
-      sgd_mom_update(pv, g[k], vv, lr, mu, wd);
+      sgd_mom_update(pv, sgd_load_g(g, k), vv, lr, mu, wd);
       v[k] = vv;
       p[k] = pv;
     }
@@ -206,7 +235,7 @@ sgd_mom_multi_f32_kernel(const SgdMultiArgs a) {
   }
   for (int k = tid; k < len; k += KS_SGD_THREADS) {
     float pv = p[k], vv = v[k];
-    sgd_mom_update(pv, g[k], vv, lr, mu, wd);
+    sgd_mom_update(pv, sgd_load_g(g, k), vv, lr, mu, wd);
     v[k] = vv;
     p[k] = pv;
   }
@@ -242,18 +271,23 @@ void sgd_momentum_(std::vector<torch::Tensor> params,
 
 // All triples in ceil(count / KS_SGD_MAX_TENSORS) launches (ResNet50: 161
 // tensors -> 2). grads[t] may be None: that tensor is skipped. Returns
-// the number of kernels launched.
-int64_t sgd_momentum_multi_(std::vector<torch::Tensor> params,
-                            std::vector<c10::optional<torch::Tensor>> grads,
-                            std::vector<torch::Tensor> momenta, double lr,
-                            double mu, double wd) {
+// the number of kernels launched. G = float: f32 gradients; G = unsigned
+// short: bf16 gradients, which must already have the parameter's strides.
+template <typename G>
+static int64_t sgd_momentum_multi_impl(
+    const std::vector<torch::Tensor>& params,
+    const std::vector<c10::optional<torch::Tensor>>& grads,
+    const std::vector<torch::Tensor>& momenta, double lr, double mu,
+    double wd) {
+  constexpr bool g_f32 = std::is_same<G, float>::value;
+  const auto gtype = g_f32 ? at::kFloat : at::kBFloat16;
   TORCH_CHECK(params.size() == grads.size() &&
                   params.size() == momenta.size(),
               "sgd_momentum_multi_: params, grads and momenta differ in "
               "length");
   auto stream = at::cuda::getCurrentCUDAStream();
   const long long max_blocks = 1LL << 30;
-  SgdMultiArgs a = {};
+  SgdMultiArgs<G> a = {};
   a.lr = (float)lr;
   a.mu = (float)mu;
   a.wd = (float)wd;
@@ -264,7 +298,7 @@ int64_t sgd_momentum_multi_(std::vector<torch::Tensor> params,
   std::vector<torch::Tensor> keep;
   auto flush = [&]() {
     if (a.count == 0) return;
-    hipLaunchKernelGGL(sgd_mom_multi_f32_kernel, dim3(a.blk[a.count]),
+    hipLaunchKernelGGL(sgd_mom_multi_f32_kernel<G>, dim3(a.blk[a.count]),
                        dim3(KS_SGD_THREADS), 0, stream.stream(), a);
     launches++;
     a.count = 0;
@@ -275,10 +309,10 @@ int64_t sgd_momentum_multi_(std::vector<torch::Tensor> params,
     auto& v = momenta[t];
     torch::Tensor g = *grads[t];
     TORCH_CHECK(g.sizes() == p.sizes() && g.is_cuda() &&
-                    g.scalar_type() == at::kFloat,
-                "sgd_momentum_multi_: f32 CUDA gradient of the "
-                "parameter's shape expected");
-    if (g.strides() != p.strides()) {
+                    g.scalar_type() == gtype,
+                "sgd_momentum_multi_: ", g_f32 ? "f32" : "bf16",
+                " CUDA gradient of the parameter's shape expected");
+    if (g_f32 && g.strides() != p.strides()) {
       // rare: e.g. a contiguous gradient for a channels-last weight
       g = at::empty_like(p).copy_(g);
       keep.push_back(g);
@@ -287,7 +321,7 @@ int64_t sgd_momentum_multi_(std::vector<torch::Tensor> params,
                     p.is_non_overlapping_and_dense() &&
                     g.sizes() == p.sizes() && g.strides() == p.strides() &&
                     v.strides() == p.strides() &&
-                    g.scalar_type() == at::kFloat &&
+                    g.scalar_type() == gtype &&
                     v.scalar_type() == at::kFloat,
                 "sgd_momentum_: f32 dense tensors with matching strides "
                 "(any memory format: the update is elementwise over the "
@@ -305,7 +339,7 @@ int64_t sgd_momentum_multi_(std::vector<torch::Tensor> params,
     if (a.count == KS_SGD_MAX_TENSORS || a.blk[a.count] + nb > max_blocks)
       flush();
     a.p[a.count] = p.data_ptr<float>();
-    a.g[a.count] = g.data_ptr<float>();
+    a.g[a.count] = static_cast<const G*>(g.data_ptr());
     a.v[a.count] = v.data_ptr<float>();
     a.n[a.count] = n;
     a.blk[a.count + 1] = a.blk[a.count] + (int)nb;
@@ -313,6 +347,23 @@ int64_t sgd_momentum_multi_(std::vector<torch::Tensor> params,
   }
   flush();
   return launches;
+}
+
+int64_t sgd_momentum_multi_(std::vector<torch::Tensor> params,
+                            std::vector<c10::optional<torch::Tensor>> grads,
+                            std::vector<torch::Tensor> momenta, double lr,
+                            double mu, double wd) {
+  return sgd_momentum_multi_impl<float>(params, grads, momenta, lr, mu, wd);
+}
+
+// The same update from bf16 gradients of the parameters' sizes and
+// strides (a bf16 ops.GradBucket's views), upcast in registers.
+int64_t sgd_momentum_multi_bf16g_(
+    std::vector<torch::Tensor> params,
+    std::vector<c10::optional<torch::Tensor>> grads,
+    std::vector<torch::Tensor> momenta, double lr, double mu, double wd) {
+  return sgd_momentum_multi_impl<unsigned short>(params, grads, momenta, lr,
+                                                 mu, wd);
 }
 
 // fused NHWC bf16 BatchNorm+ReLU (bn_relu.hip)
@@ -346,6 +397,13 @@ std::vector<torch::Tensor> bn_join_bwd(
     torch::Tensor weight_d, torch::Tensor mean, torch::Tensor invstd,
     torch::Tensor mean_d, torch::Tensor invstd_d, bool use_mask,
     bool legacy_reduce);
+
+// flat gradient bucket pack / unpack (grad_bucket.hip)
+int64_t grad_pack_multi(std::vector<c10::optional<torch::Tensor>> srcs,
+                        torch::Tensor flat, std::vector<int64_t> offsets,
+                        double scale, std::vector<torch::Tensor> like);
+int64_t grad_unpack_multi(torch::Tensor flat, std::vector<int64_t> offsets,
+                          std::vector<c10::optional<torch::Tensor>> dsts);
 
 // multi-tensor f32 <-> bf16 casts (cast.hip)
 std::vector<c10::optional<torch::Tensor>> cast_f32_to_bf16_multi(
@@ -406,6 +464,19 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "fused SGD+momentum update of all tensors in as few launches as "
         "the kernel-argument limit allows; a None gradient skips its "
         "tensor; returns the number of launches");
+  m.def("sgd_momentum_multi_bf16g_", &sgd_momentum_multi_bf16g_,
+        "sgd_momentum_multi_ reading bf16 gradients that have the "
+        "parameters' sizes and strides");
+  m.def("grad_pack_multi", &grad_pack_multi, py::arg("srcs"),
+        py::arg("flat"), py::arg("offsets"), py::arg("scale"),
+        py::arg("like"),
+        "flat[offsets[t] + i] = (f32(scale) * srcs[t][i]).to(flat.dtype) "
+        "over the storage of like[t]'s layout; None writes zeros; returns "
+        "the number of launches");
+  m.def("grad_unpack_multi", &grad_unpack_multi, py::arg("flat"),
+        py::arg("offsets"), py::arg("dsts"),
+        "dsts[t][i] = float(flat[offsets[t] + i]) over dsts[t]'s dense "
+        "storage; None is skipped; returns the number of launches");
   m.def("bn_relu_fwd_train", &bn_relu_fwd_train, py::arg("x"),
         py::arg("weight"), py::arg("bias"), py::arg("running_mean"),
         py::arg("running_var"), py::arg("momentum"), py::arg("eps"),

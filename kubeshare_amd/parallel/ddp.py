@@ -6,7 +6,10 @@ rank, LD_PRELOAD hook — and runs N ranks either one-per-GPU (the
 supported gang config) or all on ONE GPU (the hazardous config:
 two ranks sharing a device, where gating a collective would deadlock;
 kept alive by the RCCL exemption + gang co-granting + the `group`
-field of the per-UUID config file).
+field of the per-UUID config file). With fused=True the ranks train on
+the fused path (ops.fuse_model + ops.FusedSGD averaging one flat
+gradient bucket per step) instead of stock modules under
+DistributedDataParallel.
 
 Used by tools/ddp_gang.py (CLI) and tests/test_gpu_isolation.py (the
 RCCL-under-sharing hardware proof).
@@ -35,18 +38,65 @@ def _step(model, opt, x, y, autocast):
     return loss
 
 
+def _grad_dtype(grad_dtype):
+    """"f32" / "bf16" (the CLI's spelling) or a torch dtype."""
+    import torch
+    if isinstance(grad_dtype, torch.dtype):
+        return grad_dtype
+    try:
+        return {"f32": torch.float32, "bf16": torch.bfloat16}[grad_dtype]
+    except KeyError:
+        raise ValueError(f"grad_dtype {grad_dtype!r}: 'f32' or 'bf16'")
+
+
+def _check_replicas(model):
+    """Raise unless every rank holds the same parameter bits: each rank
+    packs its parameters into a bucket and sums the buffer's 32-bit
+    words into a 64-bit checksum; the checksums are all-gathered and
+    compared. A diverged gang thereby exits non-zero."""
+    import torch
+    import torch.distributed as dist
+
+    from .. import ops
+
+    params = [p.data for p in model.parameters()]
+    bucket = ops.GradBucket(params, torch.float32)
+    bucket.pack(params)
+    mine = bucket.flat.view(torch.int32).sum(dtype=torch.int64).reshape(1)
+    every = [torch.zeros_like(mine) for _ in range(dist.get_world_size())]
+    dist.all_gather(every, mine)
+    sums = [int(c.item()) for c in every]
+    if len(set(sums)) != 1:
+        raise RuntimeError(f"gang replicas diverged: rank {dist.get_rank()} "
+                           f"sees parameter checksums {sums}")
+    return sums[0]
+
+
 def ddp_worker(model_name: str = "resnet18", batch: int = 32,
                image_size: int = 224, steps: int = 10,
-               warmup: int = 3) -> float:
+               warmup: int = 3, fused: bool = False,
+               grad_dtype="f32") -> float:
     """One DDP rank: init from the torchrun/env contract, train
     `steps` timed steps, return ms/step (rank 0 also prints a
-    DDP_RESULT line)."""
+    DDP_RESULT line).
+
+    fused=True trains on the fused path instead of the stock modules
+    under DistributedDataParallel: ops.fuse_model, channels-last, bf16
+    autocast, NO DDP wrapper; ops.broadcast_parameters once, then
+    ops.FusedSGD(process_group=True, grad_dtype=...) averages the
+    gradients with one all-reduce of a flat bucket per step ("f32" or
+    "bf16" on the wire). After the timed steps the ranks compare a
+    checksum of their parameters and raise if they differ. Needs a
+    GPU."""
     import torch
     import torch.distributed as dist
 
     from ..models import build_model
 
     on_gpu = torch.cuda.is_available()
+    if fused and not on_gpu:
+        raise RuntimeError("ddp_worker(fused=True) needs a GPU: the fused "
+                           "path has no CPU kernels")
     # RCCL refuses two ranks on one device ("Duplicate GPU detected" —
     # same restriction as NCCL; the reference's own gang workloads only
     # ever put one NCCL rank per GPU, test/distribute/*). For the
@@ -58,11 +108,22 @@ def ddp_worker(model_name: str = "resnet18", batch: int = 32,
     dev = "cuda" if on_gpu else "cpu"
     if on_gpu:
         torch.cuda.set_device(0)  # ROCR_VISIBLE_DEVICES narrows the view
-    model = build_model(model_name).to(dev)
-    if on_gpu:
-        model = model.to(memory_format=torch.channels_last)
-    model = torch.nn.parallel.DistributedDataParallel(model)
-    opt = torch.optim.SGD(model.parameters(), lr=0.01, momentum=0.9)
+    if fused:
+        from .. import ops
+        from ..utils.tuning import apply_miopen_tuning
+        apply_miopen_tuning()  # before the first conv
+        model = ops.fuse_model(build_model(model_name)).to(dev).to(
+            memory_format=torch.channels_last)
+        ops.broadcast_parameters(model, src=0)
+        opt = ops.FusedSGD(model.parameters(), lr=0.01, momentum=0.9,
+                           process_group=True,
+                           grad_dtype=_grad_dtype(grad_dtype))
+    else:
+        model = build_model(model_name).to(dev)
+        if on_gpu:
+            model = model.to(memory_format=torch.channels_last)
+        model = torch.nn.parallel.DistributedDataParallel(model)
+        opt = torch.optim.SGD(model.parameters(), lr=0.01, momentum=0.9)
     x = torch.randn(batch, 3, image_size, image_size, device=dev)
     if on_gpu:
         x = x.contiguous(memory_format=torch.channels_last)
@@ -79,6 +140,8 @@ def ddp_worker(model_name: str = "resnet18", batch: int = 32,
         torch.cuda.synchronize()
     dist.barrier()
     dt = (time.perf_counter() - t0) / steps * 1000
+    if fused:
+        _check_replicas(model)
     if dist.get_rank() == 0:
         print(f"DDP_RESULT ms_per_step={dt:.2f}", flush=True)
     dist.destroy_process_group()
@@ -88,11 +151,16 @@ def ddp_worker(model_name: str = "resnet18", batch: int = 32,
 def launch_gang(ranks: int = 2, share_gpu: bool = False, steps: int = 10,
                 model: str = "resnet18", batch: int = 32,
                 image_size: int = 224, timeout: float = 300.0,
-                master_port: int = 29571):
+                master_port: int = 29571, fused: bool = False,
+                grad_dtype: str = "f32"):
     """Run a DDP gang under the full isolation chain. Returns
     (all_ok, per_gpu_stats) where per_gpu_stats is each
     LocalGPUShare's final gpu-schd STATS dict (server-side quota
-    accounting, keyed by pod)."""
+    accounting, keyed by pod). fused / grad_dtype ("f32" or "bf16")
+    are ddp_worker's: the gang trains on the fused path, and a gang
+    whose replicas diverged reports not ok."""
+    if grad_dtype not in ("f32", "bf16"):
+        raise ValueError(f"grad_dtype {grad_dtype!r}: 'f32' or 'bf16'")
     from ..isolation.local import LocalGPUShare
 
     shares, procs = [], []
@@ -132,7 +200,8 @@ def launch_gang(ranks: int = 2, share_gpu: bool = False, steps: int = 10,
             procs.append(subprocess.Popen(
                 [sys.executable, "-c",
                  "from kubeshare_amd.parallel.ddp import ddp_worker; "
-                 f"ddp_worker({model!r}, {batch}, {image_size}, {steps})"],
+                 f"ddp_worker({model!r}, {batch}, {image_size}, {steps}, "
+                 f"fused={bool(fused)}, grad_dtype={grad_dtype!r})"],
                 env=env, cwd=_REPO))
         deadline = time.time() + timeout
         for p in procs:
