@@ -13,7 +13,9 @@ With a staged weight the convolution itself goes through
 ops.conv2d_split where that op applies: the same ATen convolution, whose
 backward issues the weight gradient on a side stream. The staged
 weight's CastWeightsFn node is downstream of every such gradient and
-joins the side stream before it reads them."""
+joins the side stream before it reads them. Where ops.fuse_model has
+flagged the conv (_dgrad_fwd) the staged weight comes with its mirror,
+and conv2d_split runs the data gradient as a forward convolution."""
 import torch
 import torch.nn as nn
 
@@ -22,6 +24,11 @@ class LowpConv2d(nn.Conv2d):
     # a bf16 copy of self.weight for the forward in progress, or None
     # (plain attribute: never a parameter, a buffer or a state_dict key)
     _lowp_weight = None
+    # set by ops.fuse_model: the data gradient of this conv runs as a
+    # forward convolution of dy with _lowp_mirror, the mirrored staged
+    # weight that ops.stage_lowp_weights then provides beside _lowp_weight
+    _dgrad_fwd = False
+    _lowp_mirror = None
 
     def _split_input(self, x, w):
         """x as ops.conv2d_split takes it, or None for the stock path:
@@ -54,4 +61,5 @@ class LowpConv2d(nn.Conv2d):
             return self._conv_forward(x, w, self.bias)
         from .. import ops
         return ops.conv2d_split(xs, w, self.stride, self.padding,
-                                self.dilation, self.groups)
+                                self.dilation, self.groups,
+                                self._lowp_mirror)

@@ -706,6 +706,16 @@ def stage_lowp_weights(convs):
     wgrad_join()  # nothing of an abandoned backward runs into this step
     for m, w in zip(convs, cast_weights_bf16(weights)):
         m._lowp_weight = w
+    # one more launch mirrors the staged weight of every conv flagged by
+    # fuse_model (see dgrad_fwd_mode), for conv2d_split's data gradient
+    if torch.is_grad_enabled() and dgrad_fwd_active():
+        flagged = [m for m in convs if getattr(m, "_dgrad_fwd", False)
+                   and m.weight.requires_grad]
+        if flagged:
+            mirrors = _load().mirror_weights_multi(
+                [m._lowp_weight.detach() for m in flagged])
+            for m, wm in zip(flagged, mirrors):
+                m._lowp_mirror = wm
     return convs
 
 
@@ -713,6 +723,98 @@ def clear_lowp_weights(convs):
     """Drop the staged copies (the autograd graph keeps what it needs)."""
     for m in convs:
         m._lowp_weight = None
+        m._lowp_mirror = None
+
+
+# ----------------- stride-1 data gradients as forward convolutions
+_DGRAD_FWD_MODES = ("0", "1x1", "3x3", "all", "")
+
+
+def dgrad_fwd_mode() -> str:
+    """KUBESHARE_DGRAD_FWD selects which convs of a fused model run their
+    data gradient as a forward convolution of dy with the mirrored
+    weight (conv2d_split(mirror=...)): unset, every eligible 1x1 and 3x3
+    conv whose mirrored forward shape the model also runs as a forward
+    (see dgrad_fwd_flags); `1x1` or `3x3`, only that class under the
+    same rule; `all`, every eligible conv whatever the model contains;
+    `0`, none: no mirror launch, the stock data gradient (A/B runs,
+    operator escape hatch). fuse_model reads it when it flags the convs;
+    `0` is also honoured at every forward, and so is
+    torch.backends.cudnn.deterministic while the switch is unset
+    (dgrad_fwd_active)."""
+    v = os.environ.get("KUBESHARE_DGRAD_FWD", "")
+    if v not in _DGRAD_FWD_MODES:
+        raise ValueError(f"KUBESHARE_DGRAD_FWD={v!r}: one of 0, 1x1, 3x3, "
+                         "all expected")
+    return v
+
+
+def dgrad_fwd_active() -> bool:
+    """Whether stage_lowp_weights mirrors the flagged convs' weights for
+    the forward in progress: not under KUBESHARE_DGRAD_FWD=0, and, with
+    the switch unset, not while torch.backends.cudnn.deterministic is
+    set. The routing rests on a measurement: MIOpen's tuned forward
+    solvers beat its tuned data-gradient solvers on these shapes. With
+    the deterministic attribute MIOpen chooses among other solvers, for
+    which nothing was measured, and whoever sets it is comparing values
+    between runs or code paths (tests/test_lowp_weights_gpu.py holds
+    staged against unstaged BN gradients bitwise that way), which a dx
+    summed in another order would break for no known gain. An explicit
+    KUBESHARE_DGRAD_FWD=1x1, 3x3 or all routes regardless."""
+    import torch
+
+    mode = dgrad_fwd_mode()
+    if mode == "0":
+        return False
+    return mode != "" or not torch.backends.cudnn.deterministic
+
+
+def _dgrad_fwd_signature(m):
+    """(in, out, k) of a conv whose data gradient is a forward
+    convolution with the mirrored weight and that conv2d_split accepts
+    with one: stride 1, dilation 1, groups 1, a 1x1 or 3x3 kernel with
+    "same" zero padding, no bias. None for any other module."""
+    import torch.nn as nn
+
+    if not isinstance(m, nn.Conv2d) or m.bias is not None \
+            or m.padding_mode != "zeros" or isinstance(m.padding, str):
+        return None
+    k = m.kernel_size[0]
+    if tuple(m.kernel_size) != (k, k) or k not in (1, 3) \
+            or tuple(m.stride) != (1, 1) or tuple(m.dilation) != (1, 1) \
+            or m.groups != 1 or tuple(m.padding) != (k // 2, k // 2):
+        return None
+    return (m.in_channels, m.out_channels, k)
+
+
+def dgrad_fwd_flags(model, mode=None):
+    """{LowpConv2d: bool} for every LowpConv2d of `model`: whether its
+    data gradient is to run as a forward convolution under `mode`
+    (default: dgrad_fwd_mode()). A conv qualifies when it has a
+    _dgrad_fwd_signature and, except under `all`, the model also
+    contains a conv with the mirrored signature (in and out swapped,
+    same kernel): the mirrored forward is then a shape the model runs as
+    a forward anyway, which is the structural stand-in for "the tuned
+    MIOpen db has that forward shape". For ResNet50 that is 43 of the 53
+    convs; layer{2,3,4}.0.conv1 (forward shapes 128->256 @56, 256->512
+    @28, 512->1024 @14 are in no db), the stride-2 convs and the stem
+    stay on the stock data gradient."""
+    from ..models.conv import LowpConv2d
+
+    mode = dgrad_fwd_mode() if mode is None else mode
+    sigs = {m: _dgrad_fwd_signature(m) for m in model.modules()}
+    present = {s for s in sigs.values() if s is not None}
+    flags = {}
+    for m, sig in sigs.items():
+        if not isinstance(m, LowpConv2d):
+            continue
+        ok = sig is not None and mode != "0"
+        if ok and mode in ("1x1", "3x3"):
+            ok = mode == f"{sig[2]}x{sig[2]}"
+        if ok and mode != "all":
+            ok = (sig[1], sig[0], sig[2]) in present
+        flags[m] = ok
+    return flags
 
 
 # ------------------------------ conv weight gradients on a side stream
@@ -729,7 +831,7 @@ def wrw_stream_enabled() -> bool:
 
 
 def conv2d_split(x, w, stride=(1, 1), padding=(0, 0), dilation=(1, 1),
-                 groups=1):
+                 groups=1, mirror=None):
     """Bias-free F.conv2d(x, w, None, stride, padding, dilation, groups)
     for CUDA tensors through hip/conv_split.hip: same ATen entry, same
     MIOpen kernels, same values, but the backward issues the weight
@@ -740,11 +842,31 @@ def conv2d_split(x, w, stride=(1, 1), padding=(0, 0), dilation=(1, 1),
     until wgrad_join() has run on that stream: CastWeightsFn.backward,
     FusedSGD.step and stage_lowp_weights call it, and any other reader
     must. Inside a graph capture the backward does not fork. Double
-    backward raises."""
+    backward raises.
+
+    mirror: optionally the mirrored weight, (C,K,R,S) with
+    mirror[c,k,r,s] = w[k,c,R-1-r,S-1-s] (mirror_weights), not
+    differentiated. The backward then computes dx as the forward
+    convolution of dy with it, where MIOpen's forward kernels beat its
+    data-gradient kernels, instead of convolution_backward's data half.
+    Accepted only for bf16, stride 1, dilation 1, groups 1 and a 1x1 or
+    3x3 kernel with "same" padding; anything else raises."""
     def two(v):
         return [int(v), int(v)] if isinstance(v, int) else [int(i) for i in v]
     return _load().conv2d_split(x, w, two(stride), two(padding),
-                                two(dilation), int(groups))
+                                two(dilation), int(groups), mirror)
+
+
+def mirror_weights(weights):
+    """For each bf16 CUDA weight (K,C,R,S) of the list a new channels-last
+    (C,K,R,S) tensor with out[c,k,r,s] = in[k,c,R-1-r,S-1-s], all by one
+    launch of hip/cast.hip per 127 tensors (capturable: addresses ride in
+    the kernel arguments). A tensor that is not dense channels-last bf16
+    on the current device goes through the torch expression
+    w.flip(2, 3).transpose(0, 1).contiguous(memory_format=
+    torch.channels_last), whose values the kernel reproduces bit for
+    bit."""
+    return _load().mirror_weights_multi(list(weights))
 
 
 def wgrad_join():
@@ -1134,9 +1256,15 @@ def fuse_model(model):
     `fused_ops` flag; a flagged ResNet also stages its conv weights,
     see stage_lowp_weights; a flagged VGGPlain runs bias_relu /
     bias_relu_pool after its bias-free convs); verifies the extension
-    is importable first (fail-loud on GPU boxes)."""
+    is importable first (fail-loud on GPU boxes). A ResNet also gets its
+    LowpConv2d modules flagged for the forward-convolution data gradient
+    (_dgrad_fwd, see dgrad_fwd_flags)."""
     _load()
     for m in model.modules():
         if hasattr(m, "fused_ops"):
             m.fused_ops = True
+    from ..models.resnet import ResNet
+    if isinstance(model, ResNet):  # VGG: not measured yet (ROADMAP)
+        for m, flag in dgrad_fwd_flags(model).items():
+            m._dgrad_fwd = flag
     return model

@@ -226,3 +226,165 @@ std::vector<c10::optional<torch::Tensor>> cast_bf16_to_f32_multi(
     std::vector<c10::optional<torch::Tensor>> src) {
   return cast_multi<false>(src, "cast_bf16_to_f32_multi");
 }
+
+// ------------------------------------------------ mirrored conv weights
+//
+// mirror_weights_multi: for every bf16 weight (K,C,R,S) of a list, the
+// weight of the forward convolution that computes the stride-1 data
+// gradient: out[c,k,r,s] = in[k,c,R-1-r,S-1-s], (C,K,R,S), channels-last.
+// In memory the source is [K][R*S][C] and the result [C][R*S][K], so each
+// filter tap is a K x C -> C x K transpose between rows of R*S*C and
+// R*S*K elements, tap t landing at tap R*S-1-t. A block owns one 64 x 64
+// tile of one tap: it reads rows of the source (16 bytes per lane, eight
+// lanes per row), turns the tile in LDS and writes rows of the result the
+// same way. LDS rows are 66 elements (33 dwords, odd): the column reads
+// of the second phase touch dword (8*kv + j) * 33 + c / 2 for the lane's
+// k-vector kv = 0..7 and four values of c / 2, i.e. banks 8*kv + 0..3,
+// all distinct. The launch is cast_multi_kernel's: pointers, K, C, R*S
+// and the block prefix sum by value in the kernel arguments.
+#define KS_MIRROR_THREADS 256
+#define KS_MIRROR_TILE 64
+#define KS_MIRROR_LD (KS_MIRROR_TILE + 2)
+// 2 pointers + 4 ints per tensor, then blk[count] and count
+#define KS_MIRROR_MAX_TENSORS ((4096 - 8) / 32)
+
+struct MirrorMultiArgs {
+  const void* src[KS_MIRROR_MAX_TENSORS];
+  void* dst[KS_MIRROR_MAX_TENSORS];
+  int K[KS_MIRROR_MAX_TENSORS];
+  int C[KS_MIRROR_MAX_TENSORS];
+  int RS[KS_MIRROR_MAX_TENSORS];
+  // blk[t] = first block of tensor t; blk[count] = grid size
+  int blk[KS_MIRROR_MAX_TENSORS + 1];
+  int count;
+};
+static_assert(sizeof(MirrorMultiArgs) <= 4096,
+              "MirrorMultiArgs must fit the 4 KiB kernel-argument segment");
+static_assert(KS_MIRROR_THREADS == 4 * KS_MIRROR_TILE &&
+                  KS_MIRROR_TILE % 8 == 0,
+              "a block covers the tile in two passes of 32 rows, eight "
+              "8-element vectors per row");
+
+__global__ void __launch_bounds__(KS_MIRROR_THREADS)
+mirror_multi_kernel(const MirrorMultiArgs a) {
+  __shared__ unsigned short tile[KS_MIRROR_TILE][KS_MIRROR_LD];
+  const int b = blockIdx.x;
+  // largest t with blk[t] <= b, as in cast_multi_kernel
+  int lo = 0, hi = a.count - 1;
+  while (lo < hi) {
+    int mid = (lo + hi + 1) >> 1;
+    if (a.blk[mid] <= b) lo = mid; else hi = mid - 1;
+  }
+  const int K = a.K[lo], C = a.C[lo], RS = a.RS[lo];
+  const int tiles_c = (C + KS_MIRROR_TILE - 1) / KS_MIRROR_TILE;
+  const int tiles_k = (K + KS_MIRROR_TILE - 1) / KS_MIRROR_TILE;
+  int lb = b - a.blk[lo];  // < RS * tiles_k * tiles_c by construction
+  const int c0 = (lb % tiles_c) * KS_MIRROR_TILE;
+  lb /= tiles_c;
+  const int k0 = (lb % tiles_k) * KS_MIRROR_TILE;
+  const int tap = lb / tiles_k;
+  const long long srow = (long long)RS * C, drow = (long long)RS * K;
+  // element (k, c) of source tap RS-1-tap; element (c, k) of result tap
+  const unsigned short* __restrict__ src =
+      static_cast<const unsigned short*>(a.src[lo]) +
+      (long long)(RS - 1 - tap) * C;
+  unsigned short* __restrict__ dst =
+      static_cast<unsigned short*>(a.dst[lo]) + (long long)tap * K;
+  const int row = threadIdx.x >> 3;       // 0..31
+  const int v = (threadIdx.x & 7) * 8;    // first of the lane's 8 columns
+  // with C % 8 == 0 every row start and every v is a multiple of 8
+  // elements: 16-byte aligned exactly when the tensor is
+  const bool vin = (C & 7) == 0 && ((uintptr_t)a.src[lo] & 15) == 0;
+  const bool vout = (K & 7) == 0 && ((uintptr_t)a.dst[lo] & 15) == 0;
+#pragma unroll
+  for (int p = 0; p < 2; p++) {
+    const int k = row + p * 32;
+    const int gk = k0 + k, gc = c0 + v;
+    if (gk >= K) continue;
+    const unsigned short* s = src + gk * srow + gc;
+    if (vin) {
+      if (gc < C) {  // a vector is inside or outside as a whole
+        const cast_ushort8 x = *reinterpret_cast<const cast_ushort8*>(s);
+#pragma unroll
+        for (int j = 0; j < 8; j++) tile[k][v + j] = x[j];
+      }
+    } else {
+      for (int j = 0; j < 8; j++)
+        if (gc + j < C) tile[k][v + j] = s[j];
+    }
+  }
+  __syncthreads();
+  // only elements loaded above are read: the same bounds, transposed
+#pragma unroll
+  for (int p = 0; p < 2; p++) {
+    const int c = row + p * 32;
+    const int gc = c0 + c, gk = k0 + v;
+    if (gc >= C) continue;
+    unsigned short* d = dst + gc * drow + gk;
+    if (vout) {
+      if (gk < K) {
+        cast_ushort8 o;
+#pragma unroll
+        for (int j = 0; j < 8; j++) o[j] = tile[v + j][c];
+        *reinterpret_cast<cast_ushort8*>(d) = o;
+      }
+    } else {
+      for (int j = 0; j < 8; j++)
+        if (gk + j < K) d[j] = tile[v + j][c];
+    }
+  }
+}
+
+// The torch expression the kernel reproduces bit for bit.
+static torch::Tensor mirror_weight_eager(const torch::Tensor& w) {
+  return w.flip({2, 3}).transpose(0, 1).contiguous(
+      at::MemoryFormat::ChannelsLast);
+}
+
+std::vector<torch::Tensor> mirror_weights_multi(
+    std::vector<torch::Tensor> src) {
+  auto stream = at::cuda::getCurrentCUDAStream();
+  const long long max_blocks = 1LL << 30;
+  MirrorMultiArgs a = {};
+  a.count = 0;
+  a.blk[0] = 0;
+  auto flush = [&]() {
+    if (a.count == 0) return;
+    hipLaunchKernelGGL(mirror_multi_kernel, dim3(a.blk[a.count]),
+                       dim3(KS_MIRROR_THREADS), 0, stream.stream(), a);
+    a.count = 0;
+  };
+  std::vector<torch::Tensor> out(src.size());
+  for (size_t t = 0; t < src.size(); t++) {
+    const torch::Tensor& s = src[t];
+    TORCH_CHECK(s.defined() && s.dim() == 4,
+                "mirror_weights_multi: 4-d weights (K,C,R,S) expected");
+    if (!s.is_cuda() || s.scalar_type() != at::kBFloat16 ||
+        s.get_device() != stream.device_index() ||
+        !s.is_contiguous(at::MemoryFormat::ChannelsLast)) {
+      out[t] = mirror_weight_eager(s);
+      continue;
+    }
+    const long long K = s.size(0), C = s.size(1), RS = s.size(2) * s.size(3);
+    torch::Tensor d = at::empty(
+        {C, K, s.size(2), s.size(3)},
+        s.options().memory_format(at::MemoryFormat::ChannelsLast));
+    out[t] = d;
+    if (s.numel() == 0) continue;
+    const long long nb = RS * ((K + KS_MIRROR_TILE - 1) / KS_MIRROR_TILE) *
+                         ((C + KS_MIRROR_TILE - 1) / KS_MIRROR_TILE);
+    TORCH_CHECK(s.numel() < (1LL << 31) && nb <= max_blocks,
+                "mirror_weights_multi: tensor too large");
+    if (a.count == KS_MIRROR_MAX_TENSORS || a.blk[a.count] + nb > max_blocks)
+      flush();
+    a.src[a.count] = s.data_ptr();
+    a.dst[a.count] = d.data_ptr();
+    a.K[a.count] = (int)K;
+    a.C[a.count] = (int)C;
+    a.RS[a.count] = (int)RS;
+    a.blk[a.count + 1] = a.blk[a.count] + (int)nb;
+    a.count++;
+  }
+  flush();
+  return out;
+}

@@ -26,6 +26,13 @@
 //    wait on it
 //  - while the current stream is being captured into a graph nothing
 //    forks: both halves stay on the current stream
+//
+// Given the mirrored weight Wm[c,k,r,s] = W[k,c,R-1-r,S-1-s]
+// (mirror_weights_multi, cast.hip) the data half is the forward
+// convolution of dy with Wm instead: for stride 1 that is the same sum,
+// and MIOpen's tuned forward kernels are faster than its data-gradient
+// kernels on these shapes ("Stride-1 data gradients as
+// forward convolutions"). The weight half and everything above stay.
 #include <torch/extension.h>
 #include <ATen/cuda/CUDAContext.h>
 #include <ATen/cuda/CUDAEvent.h>
@@ -83,7 +90,8 @@ struct Conv2dSplitFn : public torch::autograd::Function<Conv2dSplitFn> {
                                torch::Tensor x, torch::Tensor w,
                                std::vector<int64_t> stride,
                                std::vector<int64_t> padding,
-                               std::vector<int64_t> dilation, int64_t groups) {
+                               std::vector<int64_t> dilation, int64_t groups,
+                               c10::optional<torch::Tensor> mirror) {
     TORCH_CHECK(x.is_cuda() && w.is_cuda() && x.dim() == 4 && w.dim() == 4,
                 "conv2d_split: 4-d CUDA tensors expected");
     TORCH_CHECK(x.get_device() == w.get_device(),
@@ -91,7 +99,36 @@ struct Conv2dSplitFn : public torch::autograd::Function<Conv2dSplitFn> {
     TORCH_CHECK(stride.size() == 2 && padding.size() == 2 &&
                     dilation.size() == 2,
                 "conv2d_split: stride, padding and dilation take two ints");
-    ctx->save_for_backward({x, w});
+    const bool routed = mirror.has_value() && mirror->defined();
+    if (routed) {
+      // the data gradient as a forward convolution of dy with the
+      // mirrored weight: an identity only for these convolutions
+      const int64_t r = w.size(2);
+      TORCH_CHECK(stride[0] == 1 && stride[1] == 1 && dilation[0] == 1 &&
+                      dilation[1] == 1 && groups == 1,
+                  "conv2d_split: a mirrored weight needs stride 1, "
+                  "dilation 1 and groups 1");
+      TORCH_CHECK(w.size(3) == r && (r == 1 || r == 3) &&
+                      padding[0] == (r - 1) / 2 && padding[1] == (r - 1) / 2,
+                  "conv2d_split: a mirrored weight needs a 1x1 or 3x3 "
+                  "kernel with \"same\" padding");
+      TORCH_CHECK(x.scalar_type() == at::kBFloat16 &&
+                      w.scalar_type() == at::kBFloat16 &&
+                      mirror->scalar_type() == at::kBFloat16,
+                  "conv2d_split: a mirrored weight needs bf16 x, w and "
+                  "mirror");
+      TORCH_CHECK(mirror->is_cuda() &&
+                      mirror->get_device() == x.get_device() &&
+                      mirror->dim() == 4 && mirror->size(0) == w.size(1) &&
+                      mirror->size(1) == w.size(0) &&
+                      mirror->size(2) == r && mirror->size(3) == r,
+                  "conv2d_split: the mirrored weight of a (K,C,R,S) weight "
+                  "is (C,K,R,S) on x's device");
+      ctx->save_for_backward({x, w, *mirror});
+    } else {
+      ctx->save_for_backward({x, w});
+    }
+    ctx->saved_data["routed"] = routed;
     ctx->saved_data["stride"] = stride;
     ctx->saved_data["padding"] = padding;
     ctx->saved_data["dilation"] = dilation;
@@ -118,7 +155,7 @@ struct Conv2dSplitFn : public torch::autograd::Function<Conv2dSplitFn> {
     const auto dilation = ctx->saved_data["dilation"].toIntVector();
     const int64_t groups = ctx->saved_data["groups"].toInt();
     torch::Tensor dx, dw;
-    const torch::autograd::variable_list none(6);
+    const torch::autograd::variable_list none(7);
     if (!dy.defined()) return none;
     const bool need_dx = ctx->needs_input_grad(0);
     const bool need_dw = ctx->needs_input_grad(1);
@@ -129,12 +166,28 @@ struct Conv2dSplitFn : public torch::autograd::Function<Conv2dSplitFn> {
           {data, !data, false});
       return data ? std::get<0>(out) : std::get<1>(out);
     };
+    // the data half: with a mirrored weight, the forward convolution of
+    // dy with it ("same" padding: R-1-p == p); dW is half(false) either way
+    const bool routed = ctx->saved_data["routed"].toBool();
+    auto data_half = [&]() {
+      if (!routed) return half(true);
+      const torch::Tensor& wm = saved[2];
+      const int64_t ph = wm.size(2) - 1 - padding[0];
+      const int64_t pw = wm.size(3) - 1 - padding[1];
+      const torch::Tensor g =
+          dy.is_contiguous(at::MemoryFormat::ChannelsLast)
+              ? dy
+              : dy.contiguous(at::MemoryFormat::ChannelsLast);
+      return at::convolution(g, wm, c10::nullopt, {1, 1}, {ph, pw}, {1, 1},
+                             /*transposed=*/false, /*output_padding=*/{0, 0},
+                             1);
+    };
     const c10::DeviceIndex dev = (c10::DeviceIndex)dy.get_device();
     c10::cuda::CUDAGuard device_guard(dev);
     if (!need_dw || capturing()) {
-      if (need_dx) dx = half(true);
+      if (need_dx) dx = data_half();
       if (need_dw) dw = half(false);
-      return {dx, dw, none[2], none[3], none[4], none[5]};
+      return {dx, dw, none[2], none[3], none[4], none[5], none[6]};
     }
     const auto cur = c10::cuda::getCurrentCUDAStream(dev);
     std::lock_guard<std::mutex> lock(g_mu);
@@ -144,7 +197,7 @@ struct Conv2dSplitFn : public torch::autograd::Function<Conv2dSplitFn> {
     // gradient waits for
     s.fork->record(cur);
     s.fork->block(side);
-    if (need_dx) dx = half(true);
+    if (need_dx) dx = data_half();
     dy.record_stream(side);
     x.record_stream(side);
     {
@@ -154,15 +207,17 @@ struct Conv2dSplitFn : public torch::autograd::Function<Conv2dSplitFn> {
     dw.record_stream(cur);
     s.done->record(side);
     s.pending = true;
-    return {dx, dw, none[2], none[3], none[4], none[5]};
+    return {dx, dw, none[2], none[3], none[4], none[5], none[6]};
   }
 };
 
 torch::Tensor conv2d_split(torch::Tensor x, torch::Tensor w,
                            std::vector<int64_t> stride,
                            std::vector<int64_t> padding,
-                           std::vector<int64_t> dilation, int64_t groups) {
-  return Conv2dSplitFn::apply(x, w, stride, padding, dilation, groups);
+                           std::vector<int64_t> dilation, int64_t groups,
+                           c10::optional<torch::Tensor> mirror) {
+  return Conv2dSplitFn::apply(x, w, stride, padding, dilation, groups,
+                              mirror);
 }
 
 // Makes the current stream of every device with a pending weight

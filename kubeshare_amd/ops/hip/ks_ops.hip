@@ -410,6 +410,9 @@ std::vector<c10::optional<torch::Tensor>> cast_f32_to_bf16_multi(
     std::vector<c10::optional<torch::Tensor>> src);
 std::vector<c10::optional<torch::Tensor>> cast_bf16_to_f32_multi(
     std::vector<c10::optional<torch::Tensor>> src);
+// mirrored bf16 conv weights, one launch per list (cast.hip)
+std::vector<torch::Tensor> mirror_weights_multi(
+    std::vector<torch::Tensor> src);
 
 // fused NHWC bf16 max-pool, one-byte argmax + gather backward (pool.hip)
 std::vector<torch::Tensor> max_pool_nhwc_fwd(torch::Tensor x, int64_t k,
@@ -451,7 +454,8 @@ std::vector<torch::Tensor> bias_relu_pool_bwd(
 torch::Tensor conv2d_split(torch::Tensor x, torch::Tensor w,
                            std::vector<int64_t> stride,
                            std::vector<int64_t> padding,
-                           std::vector<int64_t> dilation, int64_t groups);
+                           std::vector<int64_t> dilation, int64_t groups,
+                           c10::optional<torch::Tensor> mirror);
 void wgrad_join();
 bool wgrad_pending();
 
@@ -512,6 +516,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "launches as the kernel-argument limit allows; None stays None");
   m.def("cast_bf16_to_f32_multi", &cast_bf16_to_f32_multi,
         "bf16 -> f32 of every tensor of a list; None stays None");
+  m.def("mirror_weights_multi", &mirror_weights_multi,
+        "bf16 (K,C,R,S) weights -> new channels-last (C,K,R,S) tensors "
+        "with out[c,k,r,s] = in[k,c,R-1-r,S-1-s], one launch per list");
   m.def("max_pool_nhwc_fwd", &max_pool_nhwc_fwd);
   m.def("max_pool_nhwc_bwd", &max_pool_nhwc_bwd);
   m.def("bn_relu_pool_fwd_train", &bn_relu_pool_fwd_train, py::arg("x"),
@@ -539,9 +546,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("s"), py::arg("p"), "{dx, db}");
   m.def("conv2d_split", &conv2d_split, py::arg("x"), py::arg("w"),
         py::arg("stride"), py::arg("padding"), py::arg("dilation"),
-        py::arg("groups"),
+        py::arg("groups"), py::arg("mirror") = py::none(),
         "bias-free at::convolution; its backward runs the weight gradient "
-        "on a side stream (join with wgrad_join)");
+        "on a side stream (join with wgrad_join) and, given the mirrored "
+        "weight, the data gradient as a forward convolution");
   m.def("wgrad_join", &wgrad_join,
         "the current stream waits for every pending side-stream weight "
         "gradient; a no-op with nothing pending");
