@@ -7,6 +7,7 @@ paths must never silently fall back to eager PyTorch.
 """
 from __future__ import annotations
 
+import functools
 import os
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -378,12 +379,38 @@ def broadcast_parameters(model, src: int = 0, group=None):
         bucket.unpack(tensors)
 
 
+# ---------------------------------------------- shared NHWC predicates
+def _nhwc_bf16_ok(x, min_c=0, max_pixels=None) -> bool:
+    """What every fused NHWC kernel needs of an activation: 4-D, on the
+    GPU, bf16, channels-last, C % 8 == 0 and min_c <= C <= 2048 (a block
+    spans a pixel's channel groups); with max_pixels also N*H*W below it
+    (the kernels that split a pixel index into (n, h, w) keep it in 32
+    bits). The public *_supported functions add what is their own."""
+    import torch
+
+    if x.dim() != 4:
+        return False
+    n, c, h, w = x.shape
+    return (x.is_cuda and x.dtype == torch.bfloat16
+            and c % 8 == 0 and min_c <= c <= 2048
+            and (max_pixels is None or n * h * w < max_pixels)
+            and x.is_contiguous(memory_format=torch.channels_last))
+
+
+def _channels_last(dy):
+    """dy as the kernels read it: y.sum().backward() hands over a
+    stride-0 expanded gradient, and autograd promises no layout."""
+    import torch
+
+    if dy.is_contiguous(memory_format=torch.channels_last):
+        return dy
+    return dy.contiguous(memory_format=torch.channels_last)
+
+
 # ---------------------------------------------------- fused BN+ReLU(+add)
+@functools.lru_cache(maxsize=None)
 def _bn_relu_autograd():
-    """Lazily build the autograd.Function (torch import deferred)."""
-    global _BNReLUFn
-    if _BNReLUFn is not None:
-        return _BNReLUFn
+    """Build the autograd.Function once (torch import deferred)."""
     import torch
 
     class BNReLUFn(torch.autograd.Function):
@@ -462,11 +489,7 @@ def _bn_relu_autograd():
             return (dx, dres, dscale.to(ctx.wdtype), dbias.to(ctx.wdtype),
                     None, None, None, None, None, None, None)
 
-    _BNReLUFn = BNReLUFn
     return BNReLUFn
-
-
-_BNReLUFn = None
 
 
 def bn_fork_enabled() -> bool:
@@ -503,9 +526,7 @@ def bn_relu(x, bn, res=None, relu=True, fork=False):
     residual join (see BNReLUFn); the eager fall-back returns (y, y)."""
     import torch
 
-    supported = (x.dtype == torch.bfloat16 and x.size(1) % 8 == 0
-                 and x.size(1) <= 2048 and x.is_cuda
-                 and x.is_contiguous(memory_format=torch.channels_last))
+    supported = _nhwc_bf16_ok(x)
     if supported and res is not None and res.dtype != torch.bfloat16:
         # downsample-path BN runs in fp32 under autocast; the residual
         # join is bf16 in bf16 training
@@ -528,9 +549,6 @@ def bn_relu(x, bn, res=None, relu=True, fork=False):
 
 
 # ------------------------- downsample BN fused into the residual join
-_BNJoinFn = None
-
-
 def bn_join_enabled() -> bool:
     """KUBESHARE_BN_JOIN=0 runs a downsample block's join as the two ops
     bn_relu(x, bn, res=bn_relu(x_d, bn_d, relu=False)) wherever bn_join
@@ -538,11 +556,9 @@ def bn_join_enabled() -> bool:
     return os.environ.get("KUBESHARE_BN_JOIN", "1") != "0"
 
 
+@functools.lru_cache(maxsize=None)
 def _bn_join_autograd():
-    """Lazily build the autograd.Function (torch import deferred)."""
-    global _BNJoinFn
-    if _BNJoinFn is not None:
-        return _BNJoinFn
+    """Build the autograd.Function once (torch import deferred)."""
     import torch
 
     class BNJoinFn(torch.autograd.Function):
@@ -592,20 +608,14 @@ def _bn_join_autograd():
                     dbias.clone().to(ctx.wdtype_d), None, None, None, None,
                     None)
 
-    _BNJoinFn = BNJoinFn
     return BNJoinFn
 
 
 def bn_join_supported(x, x_d) -> bool:
     """True when hip/bn_join.hip covers the pair: both channels-last bf16
     on the GPU, of one shape, C % 8 == 0 and C <= 2048."""
-    import torch
-
-    return (x.dim() == 4 and x.shape == x_d.shape
-            and x.size(1) % 8 == 0 and x.size(1) <= 2048
-            and all(t.is_cuda and t.dtype == torch.bfloat16
-                    and t.is_contiguous(memory_format=torch.channels_last)
-                    for t in (x, x_d)))
+    return (x.shape == x_d.shape and _nhwc_bf16_ok(x)
+            and _nhwc_bf16_ok(x_d))
 
 
 def bn_join(x, bn, x_d, bn_d, fork=False):
@@ -620,7 +630,7 @@ def bn_join(x, bn, x_d, bn_d, fork=False):
     if not (bn_join_enabled() and bn.training and bn_d.training
             and bn_join_supported(x, x_d)):
         return bn_relu(x, bn, res=bn_relu(x_d, bn_d, relu=False), fork=fork)
-    fn = _BNJoinFn or _bn_join_autograd()
+    fn = _bn_join_autograd()
     return fn.apply(x, x_d, bn.weight, bn.bias, bn.running_mean,
                     bn.running_var, bn.momentum, bn.eps, bn_d.weight,
                     bn_d.bias, bn_d.running_mean, bn_d.running_var,
@@ -628,14 +638,9 @@ def bn_join(x, bn, x_d, bn_d, fork=False):
 
 
 # ------------------------------------------- multi-tensor weight casts
-_CastWeightsFn = None
-
-
+@functools.lru_cache(maxsize=None)
 def _cast_weights_autograd():
-    """Lazily build the autograd.Function (torch import deferred)."""
-    global _CastWeightsFn
-    if _CastWeightsFn is not None:
-        return _CastWeightsFn
+    """Build the autograd.Function once (torch import deferred)."""
     import torch
 
     class CastWeightsFn(torch.autograd.Function):
@@ -668,7 +673,6 @@ def _cast_weights_autograd():
                     out[i] = g
             return tuple(out)
 
-    _CastWeightsFn = CastWeightsFn
     return CastWeightsFn
 
 
@@ -676,7 +680,7 @@ def cast_weights_bf16(weights):
     """bf16 copies of a sequence of f32 CUDA tensors through
     CastWeightsFn (differentiable; works under no_grad and inside a
     hipGraph capture: addresses ride in the kernel arguments)."""
-    fn = _CastWeightsFn or _cast_weights_autograd()
+    fn = _cast_weights_autograd()
     return fn.apply(*weights)
 
 
@@ -879,7 +883,6 @@ def wgrad_join():
 
 # ------------------------------------------------------ fused max-pool
 _POOL_CONFIGS = ((3, 2, 1), (2, 2, 0))  # (k, s, p) compiled in pool.hip
-_MaxPoolNHWCFn = None
 
 
 def _pool_int(v):
@@ -900,17 +903,11 @@ def _pool_cfg(kernel_size, stride, padding):
 
 
 def _pool_cfg_supported(x, cfg) -> bool:
-    import torch
-
-    if cfg not in _POOL_CONFIGS or x.dim() != 4:
+    if cfg not in _POOL_CONFIGS or not _nhwc_bf16_ok(x, 8, 2 ** 31):
         return False
-    n, c, h, w = x.shape
+    n, _, h, w = x.shape
     k, _, p = cfg
-    return (x.is_cuda and x.dtype == torch.bfloat16
-            and c % 8 == 0 and 8 <= c <= 2048 and n >= 1
-            and h + 2 * p >= k and w + 2 * p >= k
-            and n * h * w < 2 ** 31
-            and x.is_contiguous(memory_format=torch.channels_last))
+    return n >= 1 and h + 2 * p >= k and w + 2 * p >= k
 
 
 def fused_pool_enabled() -> bool:
@@ -928,11 +925,9 @@ def max_pool_supported(x, kernel_size, stride=None, padding=0) -> bool:
     return _pool_cfg_supported(x, _pool_cfg(kernel_size, stride, padding))
 
 
+@functools.lru_cache(maxsize=None)
 def _max_pool_autograd():
-    """Lazily build the autograd.Function (torch import deferred)."""
-    global _MaxPoolNHWCFn
-    if _MaxPoolNHWCFn is not None:
-        return _MaxPoolNHWCFn
+    """Build the autograd.Function once (torch import deferred)."""
     import torch
     from torch.autograd.function import once_differentiable
 
@@ -955,15 +950,12 @@ def _max_pool_autograd():
         @once_differentiable
         def backward(ctx, dy):
             (idx,) = ctx.saved_tensors
-            # y.sum().backward() hands over a stride-0 expanded dy
-            if not dy.is_contiguous(memory_format=torch.channels_last):
-                dy = dy.contiguous(memory_format=torch.channels_last)
+            dy = _channels_last(dy)
             k, s, p = ctx.cfg
             dx = _load().max_pool_nhwc_bwd(dy, idx, ctx.input_sizes,
                                            k, s, p)
             return dx, None, None, None, None
 
-    _MaxPoolNHWCFn = MaxPoolNHWCFn
     return MaxPoolNHWCFn
 
 
@@ -977,14 +969,11 @@ def max_pool_nhwc(x, kernel_size, stride=None, padding=0):
         return torch.nn.functional.max_pool2d(x, kernel_size, stride,
                                               padding)
     want_idx = torch.is_grad_enabled() and x.requires_grad
-    fn = _MaxPoolNHWCFn or _max_pool_autograd()
+    fn = _max_pool_autograd()
     return fn.apply(x, *cfg, want_idx)
 
 
 # ------------------------------------------- fused BN+ReLU+max-pool
-_BNReLUMaxPoolNHWCFn = None
-
-
 def bn_pool_enabled() -> bool:
     """KUBESHARE_BN_POOL=0 runs BN+ReLU and the max-pool as two ops
     (ops.bn_relu, then ops.max_pool_nhwc) wherever bn_relu_pool would
@@ -1001,11 +990,9 @@ def bn_relu_pool_supported(x, kernel_size, stride=None, padding=0) -> bool:
     return _pool_cfg_supported(x, _pool_cfg(kernel_size, stride, padding))
 
 
+@functools.lru_cache(maxsize=None)
 def _bn_relu_pool_autograd():
-    """Lazily build the autograd.Function (torch import deferred)."""
-    global _BNReLUMaxPoolNHWCFn
-    if _BNReLUMaxPoolNHWCFn is not None:
-        return _BNReLUMaxPoolNHWCFn
+    """Build the autograd.Function once (torch import deferred)."""
     import torch
     from torch.autograd.function import once_differentiable
 
@@ -1043,16 +1030,13 @@ def _bn_relu_pool_autograd():
         @once_differentiable
         def backward(ctx, dy):
             x, idx, mean, invstd, w32, b32 = ctx.saved_tensors
-            # y.sum().backward() hands over a stride-0 expanded dy
-            if not dy.is_contiguous(memory_format=torch.channels_last):
-                dy = dy.contiguous(memory_format=torch.channels_last)
+            dy = _channels_last(dy)
             dx, dscale, dbias = _load().bn_relu_pool_bwd(
                 x, dy, idx, w32, b32, mean, invstd, *ctx.cfg,
                 ctx.legacy_reduce)
             return (dx, dscale.to(ctx.wdtype), dbias.to(ctx.wdtype)) + \
                 (None,) * 9
 
-    _BNReLUMaxPoolNHWCFn = BNReLUMaxPoolNHWCFn
     return BNReLUMaxPoolNHWCFn
 
 
@@ -1076,16 +1060,12 @@ def bn_relu_pool(x, bn, kernel_size, stride=None, padding=0):
         fused = bn.training or not want_idx
     if not fused:
         return max_pool_nhwc(bn_relu(x, bn), kernel_size, stride, padding)
-    fn = _BNReLUMaxPoolNHWCFn or _bn_relu_pool_autograd()
+    fn = _bn_relu_pool_autograd()
     return fn.apply(x, bn.weight, bn.bias, bn.running_mean, bn.running_var,
                     bn.training, bn.momentum, bn.eps, *cfg, want_idx)
 
 
 # --------------------------------------- fused bias+ReLU(+max-pool)
-_BiasReLUFn = None
-_BiasReLUMaxPoolNHWCFn = None
-
-
 def bias_relu_enabled() -> bool:
     """KUBESHARE_BIAS_RELU=0 routes flagged BN-free models
     (models.vgg.VGGPlain) back to their stock modules (A/B runs,
@@ -1098,15 +1078,10 @@ def bias_relu_supported(x) -> bool:
     """True when hip/bias_relu.hip covers bias+ReLU of x: channels-last
     bf16 on the GPU, C % 8 == 0, 8 <= C <= 2048, not empty and N*H*W
     below 2**31 (bias_relu_pool_supported minus the pool geometry)."""
-    import torch
-
-    if x.dim() != 4:
+    if not _nhwc_bf16_ok(x, 8, 2 ** 31):
         return False
-    n, c, h, w = x.shape
-    return (x.is_cuda and x.dtype == torch.bfloat16
-            and c % 8 == 0 and 8 <= c <= 2048
-            and n >= 1 and h >= 1 and w >= 1 and n * h * w < 2 ** 31
-            and x.is_contiguous(memory_format=torch.channels_last))
+    n, _, h, w = x.shape
+    return n >= 1 and h >= 1 and w >= 1
 
 
 def bias_relu_pool_supported(x, kernel_size, stride=None, padding=0) -> bool:
@@ -1116,11 +1091,9 @@ def bias_relu_pool_supported(x, kernel_size, stride=None, padding=0) -> bool:
     return _pool_cfg_supported(x, _pool_cfg(kernel_size, stride, padding))
 
 
+@functools.lru_cache(maxsize=None)
 def _bias_relu_autograd():
-    """Lazily build the autograd.Function (torch import deferred)."""
-    global _BiasReLUFn
-    if _BiasReLUFn is not None:
-        return _BiasReLUFn
+    """Build the autograd.Function once (torch import deferred)."""
     import torch
     from torch.autograd.function import once_differentiable
 
@@ -1142,21 +1115,16 @@ def _bias_relu_autograd():
         @once_differentiable
         def backward(ctx, dy):
             (y,) = ctx.saved_tensors
-            # y.sum().backward() hands over a stride-0 expanded dy
-            if not dy.is_contiguous(memory_format=torch.channels_last):
-                dy = dy.contiguous(memory_format=torch.channels_last)
+            dy = _channels_last(dy)
             dx, db = _load().bias_relu_bwd(dy, y)
             return dx, db.to(ctx.bdtype)
 
-    _BiasReLUFn = BiasReLUFn
     return BiasReLUFn
 
 
+@functools.lru_cache(maxsize=None)
 def _bias_relu_pool_autograd():
-    """Lazily build the autograd.Function (torch import deferred)."""
-    global _BiasReLUMaxPoolNHWCFn
-    if _BiasReLUMaxPoolNHWCFn is not None:
-        return _BiasReLUMaxPoolNHWCFn
+    """Build the autograd.Function once (torch import deferred)."""
     import torch
     from torch.autograd.function import once_differentiable
 
@@ -1183,14 +1151,11 @@ def _bias_relu_pool_autograd():
         @once_differentiable
         def backward(ctx, dy):
             idx, y = ctx.saved_tensors
-            # y.sum().backward() hands over a stride-0 expanded dy
-            if not dy.is_contiguous(memory_format=torch.channels_last):
-                dy = dy.contiguous(memory_format=torch.channels_last)
+            dy = _channels_last(dy)
             dx, db = _load().bias_relu_pool_bwd(dy, idx, y, ctx.input_sizes,
                                                 *ctx.cfg)
             return dx, db.to(ctx.bdtype), None, None, None, None
 
-    _BiasReLUMaxPoolNHWCFn = BiasReLUMaxPoolNHWCFn
     return BiasReLUMaxPoolNHWCFn
 
 
@@ -1207,7 +1172,7 @@ def bias_relu(x, bias):
 
     if not bias_relu_supported(x) or not bias.is_cuda:
         return torch.relu(x + bias.to(x.dtype).view(1, -1, 1, 1))
-    fn = _BiasReLUFn or _bias_relu_autograd()
+    fn = _bias_relu_autograd()
     return fn.apply(x, bias)
 
 
@@ -1230,7 +1195,7 @@ def bias_relu_pool(x, bias, kernel_size, stride=None, padding=0):
                                               padding)
     want_idx = torch.is_grad_enabled() and (x.requires_grad
                                             or bias.requires_grad)
-    fn = _BiasReLUMaxPoolNHWCFn or _bias_relu_pool_autograd()
+    fn = _bias_relu_pool_autograd()
     return fn.apply(x, bias, *cfg, want_idx)
 
 

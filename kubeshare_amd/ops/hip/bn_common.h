@@ -1,37 +1,13 @@
-// Shared between bn_relu.hip, bn_pool.hip and bn_join.hip: the bf16
-// helpers, the pinned per-element expressions, the launch geometry and
-// the host steps these translation units run (the kernels themselves
-// live in bn_relu.hip).
+// BN-specific pieces shared between bn_relu.hip, bn_pool.hip, bn_join.hip
+// and bias_relu.hip: the pinned per-element expressions, the launch
+// geometry and the host steps these translation units run (the kernels
+// themselves live in bn_relu.hip). Types, bf16 helpers, the row walk and
+// the block partials are nhwc_common.h's.
 #pragma once
-#include <hip/hip_runtime.h>
-#include <torch/extension.h>
-
-typedef __attribute__((ext_vector_type(8))) unsigned short ushort8;
-typedef __attribute__((ext_vector_type(8))) float float8;
+#include "nhwc_common.h"
 
 #define KS_BN_BLOCK 512
 #define KS_BN_UNROLL 4
-
-__device__ __forceinline__ float bf16_to_f32(unsigned short u) {
-  union {
-    unsigned int i;
-    float f;
-  } v;
-  v.i = ((unsigned int)u) << 16;
-  return v.f;
-}
-
-__device__ __forceinline__ unsigned short f32_to_bf16(float f) {
-  union {
-    float f;
-    unsigned int i;
-  } v;
-  v.f = f;
-  // round-to-nearest-even (matches PyTorch's float->bf16 cast)
-  unsigned int lsb = (v.i >> 16) & 1;
-  v.i += 0x7fffu + lsb;
-  return (unsigned short)(v.i >> 16);
-}
 
 // Forward apply, per element: y = bf16(relu(fma(x, scale', bias'))).
 // bn_apply_relu_kernel and the pooled apply (bn_pool.hip) both go

@@ -23,10 +23,9 @@
 // dbias is one sum for both BNs: the composition's downsample BN sums
 // the same terms (dres = dym) in the same order.
 //
-// Conventions are bn_relu.hip's: one lane owns 8 consecutive channels,
-// the launch geometry is bn_geom_of's, rows advance grid-stride in
-// groups of KS_BN_UNROLL, tail threads idle when C/8 does not divide the
-// block, element offsets are 64-bit. Every floating-point expression
+// Layout, row walk (NhwcRows) and block partials are nhwc_common.h's;
+// the launch geometry is bn_geom_of's and rows advance grid-stride in
+// groups of KS_BN_UNROLL. Every floating-point expression
 // goes through a pinned helper of bn_common.h, and each lane keeps its
 // rows in the composition's order and in the same groups of four, so
 // the results are the composition's bits.
@@ -34,6 +33,7 @@
 #include <torch/extension.h>
 #include <ATen/cuda/CUDAContext.h>
 
+#include <type_traits>
 #include <vector>
 
 #include "bn_common.h"
@@ -56,12 +56,9 @@ __global__ void bn_join_apply_kernel(const ushort8* __restrict__ x,
                                      const float* __restrict__ scale_d,
                                      const float* __restrict__ biasf_d,
                                      long long M, int CG) {
-  const int tid = threadIdx.x;
-  const int cg = tid % CG;
-  const int roff = tid / CG;
-  const int rows_per_blk = KS_BN_BLOCK / CG;
-  const bool active = roff < rows_per_blk;  // see bn_stats_kernel
-  const long long stride = (long long)gridDim.x * rows_per_blk;
+  const NhwcRows<KS_BN_BLOCK> rows(CG);
+  const int cg = rows.cg;
+  const long long stride = rows.stride;
   float8 s, b, sd, bd;
 #pragma unroll
   for (int j = 0; j < 8; j++) {
@@ -85,7 +82,7 @@ __global__ void bn_join_apply_kernel(const ushort8* __restrict__ x,
     }
     return o;
   };
-  long long row = active ? (long long)blockIdx.x * rows_per_blk + roff : M;
+  long long row = rows.first(M);
   for (; row + (KS_BN_UNROLL - 1) * stride < M;
        row += KS_BN_UNROLL * stride) {
     ushort8 v[KS_BN_UNROLL], vd[KS_BN_UNROLL];
@@ -133,12 +130,9 @@ __global__ void bn_join_bwd_stats_kernel(
     const float* __restrict__ invstd_d, float* __restrict__ part,
     float* __restrict__ part_d, long long M, int CG) {
   __shared__ float s_red[KS_BN_BLOCK * 8];
-  const int tid = threadIdx.x;
-  const int cg = tid % CG;
-  const int roff = tid / CG;
-  const int rows_per_blk = KS_BN_BLOCK / CG;
-  const bool active = roff < rows_per_blk;  // see bn_stats_kernel
-  const long long stride = (long long)gridDim.x * rows_per_blk;
+  const NhwcRows<KS_BN_BLOCK> rows(CG);
+  const int cg = rows.cg;
+  const long long stride = rows.stride;
   float8 mu, is, mud, isd;
 #pragma unroll
   for (int j = 0; j < 8; j++) {
@@ -150,9 +144,33 @@ __global__ void bn_join_bwd_stats_kernel(
   float8 adb = {0, 0, 0, 0, 0, 0, 0, 0};
   float8 ads = {0, 0, 0, 0, 0, 0, 0, 0};
   float8 adsd = {0, 0, 0, 0, 0, 0, 0, 0};
+  // one row; `grouped` (std::true_type inside a whole group of four
+  // rows) selects bn_acc_dscale's pattern. yv is read only without
+  // MASK, mv only with it, g2 only WITH_DY2.
+  auto one = [&](auto grouped, long long k, const ushort8& xv,
+                 const ushort8& xdv, const ushort8& yv,
+                 const unsigned char& mv, const ushort8& gv,
+                 const ushort8& g2) {
+    constexpr bool G = decltype(grouped)::value;
+    ushort8 dm;
+#pragma unroll
+    for (int j = 0; j < 8; j++) {
+      const float gin =
+          WITH_DY2 ? bn_join_grad(gv[j], g2[j]) : bf16_to_f32(gv[j]);
+      const bool on = MASK ? ((mv >> j) & 1) != 0 : bf16_to_f32(yv[j]) > 0.f;
+      const float g = on ? gin : 0.f;
+      adb[j] += g;
+      ads[j] = bn_acc_dscale<G>(
+          ads[j], g, bn_pool_xhat(bf16_to_f32(xv[j]), mu[j], is[j]), j);
+      adsd[j] = bn_acc_dscale<G>(
+          adsd[j], g, bn_pool_xhat(bf16_to_f32(xdv[j]), mud[j], isd[j]), j);
+      dm[j] = f32_to_bf16(g);
+    }
+    dym_out[k] = dm;
+  };
   constexpr int U = WITH_DY2 ? KS_BN_JOIN_U : KS_BN_JOIN_U1;
   static_assert(KS_BN_UNROLL % U == 0, "sub-batches must tile a group");
-  long long row = active ? (long long)blockIdx.x * rows_per_blk + roff : M;
+  long long row = rows.first(M);
   for (; row + (KS_BN_UNROLL - 1) * stride < M;
        row += KS_BN_UNROLL * stride) {
 #pragma unroll 1
@@ -170,26 +188,9 @@ __global__ void bn_join_bwd_stats_kernel(
         if (WITH_DY2) g2[u] = dy2[k[u]];
       }
 #pragma unroll
-      for (int u = 0; u < U; u++) {
-        ushort8 dm;
-#pragma unroll
-        for (int j = 0; j < 8; j++) {
-          const float gin = WITH_DY2 ? bn_join_grad(gv[u][j], g2[u][j])
-                                     : bf16_to_f32(gv[u][j]);
-          const bool on = MASK ? ((mv[u] >> j) & 1) != 0
-                               : bf16_to_f32(yv[u][j]) > 0.f;
-          const float g = on ? gin : 0.f;
-          adb[j] += g;
-          ads[j] = bn_acc_dscale<true>(
-              ads[j], g, bn_pool_xhat(bf16_to_f32(xv[u][j]), mu[j], is[j]),
-              j);
-          adsd[j] = bn_acc_dscale<true>(
-              adsd[j], g,
-              bn_pool_xhat(bf16_to_f32(xdv[u][j]), mud[j], isd[j]), j);
-          dm[j] = f32_to_bf16(g);
-        }
-        dym_out[k[u]] = dm;
-      }
+      for (int u = 0; u < U; u++)
+        one(std::true_type{}, k[u], xv[u], xdv[u], yv[u], mv[u], gv[u],
+            g2[u]);
     }
   }
   for (; row < M; row += stride) {
@@ -199,45 +200,17 @@ __global__ void bn_join_bwd_stats_kernel(
     unsigned char mv;
     if (MASK) mv = mask[k]; else yv = y[k];
     if (WITH_DY2) g2 = dy2[k];
-    ushort8 dm;
-#pragma unroll
-    for (int j = 0; j < 8; j++) {
-      const float gin =
-          WITH_DY2 ? bn_join_grad(gv[j], g2[j]) : bf16_to_f32(gv[j]);
-      const bool on = MASK ? ((mv >> j) & 1) != 0 : bf16_to_f32(yv[j]) > 0.f;
-      const float g = on ? gin : 0.f;
-      adb[j] += g;
-      ads[j] = bn_acc_dscale<false>(
-          ads[j], g, bn_pool_xhat(bf16_to_f32(xv[j]), mu[j], is[j]), j);
-      adsd[j] = bn_acc_dscale<false>(
-          adsd[j], g, bn_pool_xhat(bf16_to_f32(xdv[j]), mud[j], isd[j]), j);
-      dm[j] = f32_to_bf16(g);
-    }
-    dym_out[k] = dm;
+    one(std::false_type{}, k, xv, xdv, yv, mv, gv, g2);
   }
 
-  // LDS tree over the lanes sharing a channel group (bn_stats_kernel's),
-  // once per sum: part[0] = dbias, part[1] = dscale, part_d = dscale_d
+  // part[0] = dbias, part[1] = dscale, part_d = dscale_d
   const int C = CG * 8;
-  float* const outs[3] = {part + (long long)blockIdx.x * C,
-                          part + (long long)(gridDim.x + blockIdx.x) * C,
-                          part_d + (long long)blockIdx.x * C};
-#pragma unroll
-  for (int q = 0; q < 3; q++) {
-    const float8& a = q == 0 ? adb : q == 1 ? ads : adsd;
-    if (q) __syncthreads();
-#pragma unroll
-    for (int j = 0; j < 8; j++) s_red[tid * 8 + j] = a[j];
-    __syncthreads();
-    if (tid < CG) {
-      float8 t = {0, 0, 0, 0, 0, 0, 0, 0};
-      for (int r = 0; r < rows_per_blk; r++)
-#pragma unroll
-        for (int j = 0; j < 8; j++) t[j] += s_red[(r * CG + tid) * 8 + j];
-#pragma unroll
-      for (int j = 0; j < 8; j++) outs[q][tid * 8 + j] = t[j];
-    }
-  }
+  nhwc_block_partials<KS_BN_BLOCK>(s_red, adb, part, CG);
+  __syncthreads();
+  nhwc_block_partials<KS_BN_BLOCK>(s_red, ads,
+                                   part + (long long)gridDim.x * C, CG);
+  __syncthreads();
+  nhwc_block_partials<KS_BN_BLOCK>(s_red, adsd, part_d, CG);
 }
 
 // --------------------------------------------------------- bwd apply
@@ -255,12 +228,9 @@ __global__ void bn_join_bwd_apply_kernel(
     const float* __restrict__ weight_d, const float* __restrict__ dbias,
     const float* __restrict__ dscale, const float* __restrict__ dscale_d,
     long long M, int CG) {
-  const int tid = threadIdx.x;
-  const int cg = tid % CG;
-  const int roff = tid / CG;
-  const int rows_per_blk = KS_BN_BLOCK / CG;
-  const bool active = roff < rows_per_blk;
-  const long long stride = (long long)gridDim.x * rows_per_blk;
+  const NhwcRows<KS_BN_BLOCK> rows(CG);
+  const int cg = rows.cg;
+  const long long stride = rows.stride;
   const float invM = 1.f / (float)M;
   float8 mu, is, w, ds, mud, isd, wd, dsd, db;
 #pragma unroll
@@ -276,8 +246,24 @@ __global__ void bn_join_bwd_apply_kernel(
     dsd[j] = dscale_d[c] * invM;
     db[j] = dbias[c] * invM;
   }
+  auto one = [&](long long k, const ushort8& xv, const ushort8& xdv,
+                 const ushort8& gv) {
+    ushort8 o, od;
+#pragma unroll
+    for (int j = 0; j < 8; j++) {
+      const float g = bf16_to_f32(gv[j]);  // already ReLU-masked
+      o[j] = f32_to_bf16(bn_pool_dx(
+          w[j], g, db[j], bn_pool_xhat(bf16_to_f32(xv[j]), mu[j], is[j]),
+          ds[j]));
+      od[j] = f32_to_bf16(bn_pool_dx(
+          wd[j], g, db[j],
+          bn_pool_xhat(bf16_to_f32(xdv[j]), mud[j], isd[j]), dsd[j]));
+    }
+    dx[k] = o;
+    dxd[k] = od;
+  };
   constexpr int U = KS_BN_JOIN_UA;
-  long long row = active ? (long long)blockIdx.x * rows_per_blk + roff : M;
+  long long row = rows.first(M);
   for (; row + (U - 1) * stride < M; row += U * stride) {
     ushort8 xv[U], xdv[U], gv[U];
     long long k[U];
@@ -289,38 +275,12 @@ __global__ void bn_join_bwd_apply_kernel(
       gv[u] = dym[k[u]];
     }
 #pragma unroll
-    for (int u = 0; u < U; u++) {
-      ushort8 o, od;
-#pragma unroll
-      for (int j = 0; j < 8; j++) {
-        const float g = bf16_to_f32(gv[u][j]);  // already ReLU-masked
-        o[j] = f32_to_bf16(bn_pool_dx(
-            w[j], g, db[j],
-            bn_pool_xhat(bf16_to_f32(xv[u][j]), mu[j], is[j]), ds[j]));
-        od[j] = f32_to_bf16(bn_pool_dx(
-            wd[j], g, db[j],
-            bn_pool_xhat(bf16_to_f32(xdv[u][j]), mud[j], isd[j]), dsd[j]));
-      }
-      dx[k[u]] = o;
-      dxd[k[u]] = od;
-    }
+    for (int u = 0; u < U; u++) one(k[u], xv[u], xdv[u], gv[u]);
   }
   for (; row < M; row += stride) {
     const long long k = row * CG + cg;
     const ushort8 xv = x[k], xdv = xd[k], gv = dym[k];
-    ushort8 o, od;
-#pragma unroll
-    for (int j = 0; j < 8; j++) {
-      const float g = bf16_to_f32(gv[j]);
-      o[j] = f32_to_bf16(bn_pool_dx(
-          w[j], g, db[j], bn_pool_xhat(bf16_to_f32(xv[j]), mu[j], is[j]),
-          ds[j]));
-      od[j] = f32_to_bf16(bn_pool_dx(
-          wd[j], g, db[j],
-          bn_pool_xhat(bf16_to_f32(xdv[j]), mud[j], isd[j]), dsd[j]));
-    }
-    dx[k] = o;
-    dxd[k] = od;
+    one(k, xv, xdv, gv);
   }
 }
 
@@ -333,14 +293,6 @@ void check_pair(const torch::Tensor& x, const torch::Tensor& x_d,
                   x_d.scalar_type() == at::kBFloat16 &&
                   x_d.is_contiguous(at::MemoryFormat::ChannelsLast),
               what, ": x_d must be channels-last bf16 of x's shape");
-}
-
-const ushort8* cptr(const torch::Tensor& t) {
-  return reinterpret_cast<const ushort8*>(t.data_ptr());
-}
-
-ushort8* mptr(torch::Tensor& t) {
-  return reinterpret_cast<ushort8*>(t.data_ptr());
 }
 
 }  // namespace
@@ -377,7 +329,8 @@ std::vector<torch::Tensor> bn_join_fwd_train(
                      x.options().dtype(at::kByte));
   auto launch = [&](auto kern) {
     hipLaunchKernelGGL(kern, dim3(g.blocks), dim3(KS_BN_BLOCK), 0,
-                       stream.stream(), cptr(x), cptr(x_d), mptr(y),
+                       stream.stream(), nhwc_cptr(x), nhwc_cptr(x_d),
+                       nhwc_mptr(y),
                        want_mask ? mask.data_ptr<unsigned char>() : nullptr,
                        scale.data_ptr<float>(), biasf.data_ptr<float>(),
                        scale_d.data_ptr<float>(), biasf_d.data_ptr<float>(),
@@ -431,9 +384,10 @@ std::vector<torch::Tensor> bn_join_bwd(
   auto launch_stats = [&](auto kern) {
     hipLaunchKernelGGL(
         kern, dim3(g.stat_blocks), dim3(KS_BN_BLOCK), 0, stream.stream(),
-        cptr(x), cptr(x_d), use_mask ? nullptr : cptr(y_or_mask),
-        use_mask ? y_or_mask.data_ptr<unsigned char>() : nullptr, cptr(dy),
-        fold_dy2 ? cptr(*dy2) : nullptr, mptr(dym), mean.data_ptr<float>(),
+        nhwc_cptr(x), nhwc_cptr(x_d), use_mask ? nullptr : nhwc_cptr(y_or_mask),
+        use_mask ? y_or_mask.data_ptr<unsigned char>() : nullptr, nhwc_cptr(dy),
+        fold_dy2 ? nhwc_cptr(*dy2) : nullptr, nhwc_mptr(dym),
+        mean.data_ptr<float>(),
         invstd.data_ptr<float>(), mean_d.data_ptr<float>(),
         invstd_d.data_ptr<float>(), part_p, part_d_p, g.M, g.CG);
   };
@@ -448,8 +402,9 @@ std::vector<torch::Tensor> bn_join_bwd(
   bn_launch_reduce_one(part_d_p, g.stat_blocks, g.C, dscale_d_p,
                        stream.stream());
   hipLaunchKernelGGL(bn_join_bwd_apply_kernel, dim3(g.blocks),
-                     dim3(KS_BN_BLOCK), 0, stream.stream(), cptr(x),
-                     cptr(x_d), cptr(dym), mptr(dx), mptr(dx_d),
+                     dim3(KS_BN_BLOCK), 0, stream.stream(), nhwc_cptr(x),
+                     nhwc_cptr(x_d), nhwc_cptr(dym), nhwc_mptr(dx),
+                     nhwc_mptr(dx_d),
                      mean.data_ptr<float>(), invstd.data_ptr<float>(),
                      weight.data_ptr<float>(), mean_d.data_ptr<float>(),
                      invstd_d.data_ptr<float>(), weight_d.data_ptr<float>(),

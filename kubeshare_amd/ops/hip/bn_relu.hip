@@ -22,6 +22,9 @@
 //    per-channel global atomics (2*C atomics x 2048 blocks measured as
 //    ~0.4 ms of fixed cost per BN call).
 //  - all stats/parameter math in f32; tensors read/written as bf16x8.
+//  - the row walk with its idle-tail rule (NhwcRows) and the LDS tree of
+//    the block partials (nhwc_block_partials) are nhwc_common.h's; each
+//    kernel writes its per-row arithmetic once, as `one(...)`.
 //
 // Launch sequence (three launches each):
 //   forward   bn_stats -> bn_reduce_tile<FINALIZE> -> bn_apply_relu
@@ -40,10 +43,12 @@
 #include <torch/extension.h>
 #include <ATen/cuda/CUDAContext.h>
 
+#include <type_traits>
 #include <vector>
 
-// types, bf16 helpers, KS_BN_BLOCK / KS_BN_UNROLL, the pinned
-// per-element expressions and the host steps shared with bn_pool.hip
+// KS_BN_BLOCK / KS_BN_UNROLL, the pinned per-element expressions and the
+// host steps shared with the other BN files; through it nhwc_common.h:
+// types, bf16 helpers, the row walk (NhwcRows) and the block partials
 #include "bn_common.h"
 
 #define KS_BN_UNROLL_STATS 8
@@ -57,18 +62,21 @@ __global__ void bn_stats_kernel(const ushort8* __restrict__ x,
                                 float* __restrict__ part,
                                 long long M, int CG) {
   __shared__ float s_red[KS_BN_BLOCK * 8];
-  const int tid = threadIdx.x;
-  const int cg = tid % CG;
-  const int roff = tid / CG;
-  const int rows_per_blk = KS_BN_BLOCK / CG;
-  // when CG does not divide the block, the tail threads would alias the
-  // NEXT block's rows — they must idle (their LDS slots stay zero)
-  const bool active = roff < rows_per_blk;
-  const long long stride = (long long)gridDim.x * rows_per_blk;
+  const NhwcRows<KS_BN_BLOCK> rows(CG);
+  const int cg = rows.cg;
+  const long long stride = rows.stride;
 
   float8 acc = {0, 0, 0, 0, 0, 0, 0, 0};
   float8 acc2 = {0, 0, 0, 0, 0, 0, 0, 0};
-  long long row = active ? (long long)blockIdx.x * rows_per_blk + roff : M;
+  auto one = [&](const ushort8& v) {
+#pragma unroll
+    for (int j = 0; j < 8; j++) {
+      float f = bf16_to_f32(v[j]);
+      acc[j] += f;
+      acc2[j] += f * f;
+    }
+  };
+  long long row = rows.first(M);
   // unrolled main loop: KS_BN_UNROLL_STATS independent loads in flight
   for (; row + (KS_BN_UNROLL_STATS - 1) * stride < M;
        row += KS_BN_UNROLL_STATS * stride) {
@@ -77,51 +85,18 @@ __global__ void bn_stats_kernel(const ushort8* __restrict__ x,
     for (int u = 0; u < KS_BN_UNROLL_STATS; u++)
       v[u] = x[(row + u * stride) * CG + cg];
 #pragma unroll
-    for (int u = 0; u < KS_BN_UNROLL_STATS; u++)
-#pragma unroll
-      for (int j = 0; j < 8; j++) {
-        float f = bf16_to_f32(v[u][j]);
-        acc[j] += f;
-        acc2[j] += f * f;
-      }
+    for (int u = 0; u < KS_BN_UNROLL_STATS; u++) one(v[u]);
   }
   for (; row < M; row += stride) {
     ushort8 v = x[row * CG + cg];
-#pragma unroll
-    for (int j = 0; j < 8; j++) {
-      float f = bf16_to_f32(v[j]);
-      acc[j] += f;
-      acc2[j] += f * f;
-    }
+    one(v);
   }
 
   const int C = CG * 8;
-  float* sum_part = part + (long long)blockIdx.x * C;
-  float* sq_part = part + (long long)(gridDim.x + blockIdx.x) * C;
-  // LDS tree over the lanes sharing a channel group, then plain stores
-#pragma unroll
-  for (int j = 0; j < 8; j++) s_red[tid * 8 + j] = acc[j];
+  nhwc_block_partials<KS_BN_BLOCK>(s_red, acc, part, CG);
   __syncthreads();
-  if (tid < CG) {
-    float8 t = {0, 0, 0, 0, 0, 0, 0, 0};
-    for (int r = 0; r < rows_per_blk; r++)
-#pragma unroll
-      for (int j = 0; j < 8; j++) t[j] += s_red[(r * CG + tid) * 8 + j];
-#pragma unroll
-    for (int j = 0; j < 8; j++) sum_part[tid * 8 + j] = t[j];
-  }
-  __syncthreads();
-#pragma unroll
-  for (int j = 0; j < 8; j++) s_red[tid * 8 + j] = acc2[j];
-  __syncthreads();
-  if (tid < CG) {
-    float8 t = {0, 0, 0, 0, 0, 0, 0, 0};
-    for (int r = 0; r < rows_per_blk; r++)
-#pragma unroll
-      for (int j = 0; j < 8; j++) t[j] += s_red[(r * CG + tid) * 8 + j];
-#pragma unroll
-    for (int j = 0; j < 8; j++) sq_part[tid * 8 + j] = t[j];
-  }
+  nhwc_block_partials<KS_BN_BLOCK>(s_red, acc2,
+                                   part + (long long)gridDim.x * C, CG);
 }
 
 // ---------------------------------------- partial reduction (legacy)
@@ -332,46 +307,17 @@ __global__ void bn_apply_relu_kernel(const ushort8* __restrict__ x,
                                      const float* __restrict__ scale,
                                      const float* __restrict__ biasf,
                                      long long M, int CG) {
-  const int tid = threadIdx.x;
-  const int cg = tid % CG;
-  const int roff = tid / CG;
-  const int rows_per_blk = KS_BN_BLOCK / CG;
-  const bool active = roff < rows_per_blk;  // see bn_stats_kernel
-  const long long stride = (long long)gridDim.x * rows_per_blk;
+  const NhwcRows<KS_BN_BLOCK> rows(CG);
+  const int cg = rows.cg;
+  const long long stride = rows.stride;
   float8 s, b;
 #pragma unroll
   for (int j = 0; j < 8; j++) {
     s[j] = scale[cg * 8 + j];
     b[j] = biasf[cg * 8 + j];
   }
-  long long row = active ? (long long)blockIdx.x * rows_per_blk + roff : M;
-  for (; row + (KS_BN_UNROLL - 1) * stride < M;
-       row += KS_BN_UNROLL * stride) {
-    ushort8 v[KS_BN_UNROLL], r[KS_BN_UNROLL], o[KS_BN_UNROLL];
-    long long k[KS_BN_UNROLL];
-#pragma unroll
-    for (int u = 0; u < KS_BN_UNROLL; u++) {
-      k[u] = (row + u * stride) * CG + cg;
-      v[u] = x[k[u]];
-      if (WITH_RES) r[u] = res[k[u]];
-    }
-#pragma unroll
-    for (int u = 0; u < KS_BN_UNROLL; u++) {
-#pragma unroll
-      for (int j = 0; j < 8; j++) {
-        float f = bn_affine(bf16_to_f32(v[u][j]), s[j], b[j]);
-        if (WITH_RES) f += bf16_to_f32(r[u][j]);
-        o[u][j] = RELU ? bn_relu_bf16(f) : f32_to_bf16(f);
-      }
-      y[k[u]] = o[u];
-      if (MASK) mask[k[u]] = bn_mask_byte(o[u]);
-    }
-  }
-  for (; row < M; row += stride) {
-    const long long k = row * CG + cg;
-    ushort8 v = x[k];
-    ushort8 r;
-    if (WITH_RES) r = res[k];
+  // one row: r is read only WITH_RES
+  auto one = [&](long long k, const ushort8& v, const ushort8& r) {
     ushort8 o;
 #pragma unroll
     for (int j = 0; j < 8; j++) {
@@ -381,6 +327,27 @@ __global__ void bn_apply_relu_kernel(const ushort8* __restrict__ x,
     }
     y[k] = o;
     if (MASK) mask[k] = bn_mask_byte(o);
+  };
+  long long row = rows.first(M);
+  for (; row + (KS_BN_UNROLL - 1) * stride < M;
+       row += KS_BN_UNROLL * stride) {
+    ushort8 v[KS_BN_UNROLL], r[KS_BN_UNROLL];
+    long long k[KS_BN_UNROLL];
+#pragma unroll
+    for (int u = 0; u < KS_BN_UNROLL; u++) {
+      k[u] = (row + u * stride) * CG + cg;
+      v[u] = x[k[u]];
+      if (WITH_RES) r[u] = res[k[u]];
+    }
+#pragma unroll
+    for (int u = 0; u < KS_BN_UNROLL; u++) one(k[u], v[u], r[u]);
+  }
+  for (; row < M; row += stride) {
+    const long long k = row * CG + cg;
+    ushort8 v = x[k];
+    ushort8 r;
+    if (WITH_RES) r = res[k];
+    one(k, v, r);
   }
 }
 
@@ -408,12 +375,9 @@ __global__ void bn_bwd_stats_kernel(const ushort8* __restrict__ x,
                                     float* __restrict__ part,
                                     long long M, int CG) {
   __shared__ float s_red[KS_BN_BLOCK * 8];
-  const int tid = threadIdx.x;
-  const int cg = tid % CG;
-  const int roff = tid / CG;
-  const int rows_per_blk = KS_BN_BLOCK / CG;
-  const bool active = roff < rows_per_blk;  // see bn_stats_kernel
-  const long long stride = (long long)gridDim.x * rows_per_blk;
+  const NhwcRows<KS_BN_BLOCK> rows(CG);
+  const int cg = rows.cg;
+  const long long stride = rows.stride;
   float8 mu, is;
 #pragma unroll
   for (int j = 0; j < 8; j++) {
@@ -422,6 +386,25 @@ __global__ void bn_bwd_stats_kernel(const ushort8* __restrict__ x,
   }
   float8 adb = {0, 0, 0, 0, 0, 0, 0, 0};
   float8 ads = {0, 0, 0, 0, 0, 0, 0, 0};
+  // one row; `grouped` (std::true_type inside a whole group of four
+  // rows) selects bn_acc_dscale's pattern. yv is read only without
+  // MASK, mv only with it, g2 only WITH_DY2.
+  auto one = [&](auto grouped, long long k, const ushort8& xv,
+                 const ushort8& yv, const unsigned char& mv,
+                 const ushort8& gv, const ushort8& g2) {
+    ushort8 dm;
+#pragma unroll
+    for (int j = 0; j < 8; j++) {
+      float gin = WITH_DY2 ? bn_join_grad(gv[j], g2[j]) : bf16_to_f32(gv[j]);
+      const bool on = MASK ? ((mv >> j) & 1) != 0 : bf16_to_f32(yv[j]) > 0.f;
+      float g = on ? gin : 0.f;
+      float xhat = (bf16_to_f32(xv[j]) - mu[j]) * is[j];
+      adb[j] += g;
+      ads[j] = bn_acc_dscale<decltype(grouped)::value>(ads[j], g, xhat, j);
+      if (WRITE_DYM) dm[j] = f32_to_bf16(g);
+    }
+    if (WRITE_DYM) dym_out[k] = dm;
+  };
   // Rows advance in groups of KS_BN_UNROLL; a group is loaded U rows at
   // a time. The two-gradient variant reads four tensors per row instead
   // of three, and at U = KS_BN_UNROLL it spills (112 B/lane of scratch
@@ -430,7 +413,7 @@ __global__ void bn_bwd_stats_kernel(const ushort8* __restrict__ x,
   // at two rows; the one-gradient y-reading variant is left as it was)
   constexpr int U = (WITH_DY2 || MASK) ? KS_BN_UNROLL_DY2 : KS_BN_UNROLL;
   static_assert(KS_BN_UNROLL % U == 0, "sub-batches must tile a group");
-  long long row = active ? (long long)blockIdx.x * rows_per_blk + roff : M;
+  long long row = rows.first(M);
   for (; row + (KS_BN_UNROLL - 1) * stride < M;
        row += KS_BN_UNROLL * stride) {
     // a real loop: unrolled, the scheduler hoists the next sub-batch's
@@ -450,22 +433,8 @@ __global__ void bn_bwd_stats_kernel(const ushort8* __restrict__ x,
         if (WITH_DY2) g2[u] = dy2[k[u]];
       }
 #pragma unroll
-      for (int u = 0; u < U; u++) {
-        ushort8 dm;
-#pragma unroll
-        for (int j = 0; j < 8; j++) {
-          float gin = WITH_DY2 ? bn_join_grad(gv[u][j], g2[u][j])
-                               : bf16_to_f32(gv[u][j]);
-          const bool on = MASK ? ((mv[u] >> j) & 1) != 0
-                               : bf16_to_f32(yv[u][j]) > 0.f;
-          float g = on ? gin : 0.f;
-          float xhat = (bf16_to_f32(xv[u][j]) - mu[j]) * is[j];
-          adb[j] += g;
-          ads[j] = bn_acc_dscale<true>(ads[j], g, xhat, j);
-          if (WRITE_DYM) dm[j] = f32_to_bf16(g);
-        }
-        if (WRITE_DYM) dym_out[k[u]] = dm;
-      }
+      for (int u = 0; u < U; u++)
+        one(std::true_type{}, k[u], xv[u], yv[u], mv[u], gv[u], g2[u]);
     }
   }
   for (; row < M; row += stride) {
@@ -476,46 +445,14 @@ __global__ void bn_bwd_stats_kernel(const ushort8* __restrict__ x,
     if (MASK) mv = mask[k]; else yv = y[k];
     ushort8 g2;
     if (WITH_DY2) g2 = dy2[k];
-    ushort8 dm;
-#pragma unroll
-    for (int j = 0; j < 8; j++) {
-      float gin = WITH_DY2 ? bn_join_grad(gv[j], g2[j]) : bf16_to_f32(gv[j]);
-      const bool on = MASK ? ((mv >> j) & 1) != 0 : bf16_to_f32(yv[j]) > 0.f;
-      float g = on ? gin : 0.f;
-      float xhat = (bf16_to_f32(xv[j]) - mu[j]) * is[j];
-      adb[j] += g;
-      ads[j] = bn_acc_dscale<false>(ads[j], g, xhat, j);
-      if (WRITE_DYM) dm[j] = f32_to_bf16(g);
-    }
-    if (WRITE_DYM) dym_out[k] = dm;
+    one(std::false_type{}, k, xv, yv, mv, gv, g2);
   }
 
   const int C = CG * 8;
-  float* db_part = part + (long long)blockIdx.x * C;
-  float* ds_part = part + (long long)(gridDim.x + blockIdx.x) * C;
-#pragma unroll
-  for (int j = 0; j < 8; j++) s_red[tid * 8 + j] = adb[j];
+  nhwc_block_partials<KS_BN_BLOCK>(s_red, adb, part, CG);
   __syncthreads();
-  if (tid < CG) {
-    float8 t = {0, 0, 0, 0, 0, 0, 0, 0};
-    for (int r = 0; r < rows_per_blk; r++)
-#pragma unroll
-      for (int j = 0; j < 8; j++) t[j] += s_red[(r * CG + tid) * 8 + j];
-#pragma unroll
-    for (int j = 0; j < 8; j++) db_part[tid * 8 + j] = t[j];
-  }
-  __syncthreads();
-#pragma unroll
-  for (int j = 0; j < 8; j++) s_red[tid * 8 + j] = ads[j];
-  __syncthreads();
-  if (tid < CG) {
-    float8 t = {0, 0, 0, 0, 0, 0, 0, 0};
-    for (int r = 0; r < rows_per_blk; r++)
-#pragma unroll
-      for (int j = 0; j < 8; j++) t[j] += s_red[(r * CG + tid) * 8 + j];
-#pragma unroll
-    for (int j = 0; j < 8; j++) ds_part[tid * 8 + j] = t[j];
-  }
+  nhwc_block_partials<KS_BN_BLOCK>(s_red, ads,
+                                   part + (long long)gridDim.x * C, CG);
 }
 
 // ----------------------------------------- bwd stats, no-y variant
@@ -534,12 +471,9 @@ __global__ void bn_bwd_stats_noy_kernel(const ushort8* __restrict__ x,
                                         float* __restrict__ part,
                                         long long M, int CG) {
   __shared__ float s_red[KS_BN_BLOCK * 8];
-  const int tid = threadIdx.x;
-  const int cg = tid % CG;
-  const int roff = tid / CG;
-  const int rows_per_blk = KS_BN_BLOCK / CG;
-  const bool active = roff < rows_per_blk;  // see bn_stats_kernel
-  const long long stride = (long long)gridDim.x * rows_per_blk;
+  const NhwcRows<KS_BN_BLOCK> rows(CG);
+  const int cg = rows.cg;
+  const long long stride = rows.stride;
   float8 mu, is, sc, bf;
 #pragma unroll
   for (int j = 0; j < 8; j++) {
@@ -551,7 +485,21 @@ __global__ void bn_bwd_stats_noy_kernel(const ushort8* __restrict__ x,
   }
   float8 adb = {0, 0, 0, 0, 0, 0, 0, 0};
   float8 ads = {0, 0, 0, 0, 0, 0, 0, 0};
-  long long row = active ? (long long)blockIdx.x * rows_per_blk + roff : M;
+  auto one = [&](const ushort8& xv, const ushort8& gv) {
+#pragma unroll
+    for (int j = 0; j < 8; j++) {
+      float xf = bf16_to_f32(xv[j]);
+      float g = bf16_to_f32(gv[j]);
+      if (RELU) {
+        // exact fwd replication: y stored as bf16(relu(f))
+        float f = fmaf(xf, sc[j], bf[j]);
+        if (!f32_to_bf16(f > 0.f ? f : 0.f)) g = 0.f;
+      }
+      adb[j] += g;
+      ads[j] += g * ((xf - mu[j]) * is[j]);
+    }
+  };
+  long long row = rows.first(M);
   for (; row + (KS_BN_UNROLL - 1) * stride < M;
        row += KS_BN_UNROLL * stride) {
     ushort8 xv[KS_BN_UNROLL], gv[KS_BN_UNROLL];
@@ -562,62 +510,19 @@ __global__ void bn_bwd_stats_noy_kernel(const ushort8* __restrict__ x,
       gv[u] = dy[k];
     }
 #pragma unroll
-    for (int u = 0; u < KS_BN_UNROLL; u++)
-#pragma unroll
-      for (int j = 0; j < 8; j++) {
-        float xf = bf16_to_f32(xv[u][j]);
-        float g = bf16_to_f32(gv[u][j]);
-        if (RELU) {
-          // exact fwd replication: y stored as bf16(relu(f))
-          float f = fmaf(xf, sc[j], bf[j]);
-          if (!f32_to_bf16(f > 0.f ? f : 0.f)) g = 0.f;
-        }
-        adb[j] += g;
-        ads[j] += g * ((xf - mu[j]) * is[j]);
-      }
+    for (int u = 0; u < KS_BN_UNROLL; u++) one(xv[u], gv[u]);
   }
   for (; row < M; row += stride) {
     const long long k = row * CG + cg;
     ushort8 xv = x[k], gv = dy[k];
-#pragma unroll
-    for (int j = 0; j < 8; j++) {
-      float xf = bf16_to_f32(xv[j]);
-      float g = bf16_to_f32(gv[j]);
-      if (RELU) {
-        float f = fmaf(xf, sc[j], bf[j]);
-        if (!f32_to_bf16(f > 0.f ? f : 0.f)) g = 0.f;
-      }
-      adb[j] += g;
-      ads[j] += g * ((xf - mu[j]) * is[j]);
-    }
+    one(xv, gv);
   }
 
   const int C = CG * 8;
-  float* db_part = part + (long long)blockIdx.x * C;
-  float* ds_part = part + (long long)(gridDim.x + blockIdx.x) * C;
-#pragma unroll
-  for (int j = 0; j < 8; j++) s_red[tid * 8 + j] = adb[j];
+  nhwc_block_partials<KS_BN_BLOCK>(s_red, adb, part, CG);
   __syncthreads();
-  if (tid < CG) {
-    float8 t = {0, 0, 0, 0, 0, 0, 0, 0};
-    for (int r = 0; r < rows_per_blk; r++)
-#pragma unroll
-      for (int j = 0; j < 8; j++) t[j] += s_red[(r * CG + tid) * 8 + j];
-#pragma unroll
-    for (int j = 0; j < 8; j++) db_part[tid * 8 + j] = t[j];
-  }
-  __syncthreads();
-#pragma unroll
-  for (int j = 0; j < 8; j++) s_red[tid * 8 + j] = ads[j];
-  __syncthreads();
-  if (tid < CG) {
-    float8 t = {0, 0, 0, 0, 0, 0, 0, 0};
-    for (int r = 0; r < rows_per_blk; r++)
-#pragma unroll
-      for (int j = 0; j < 8; j++) t[j] += s_red[(r * CG + tid) * 8 + j];
-#pragma unroll
-    for (int j = 0; j < 8; j++) ds_part[tid * 8 + j] = t[j];
-  }
+  nhwc_block_partials<KS_BN_BLOCK>(s_red, ads,
+                                   part + (long long)gridDim.x * C, CG);
 }
 
 // ----------------------------------------- bwd apply, no-y variant
@@ -632,12 +537,9 @@ __global__ void bn_bwd_apply_noy_kernel(const ushort8* __restrict__ x,
                                         const float* __restrict__ dbias,
                                         const float* __restrict__ dscale,
                                         long long M, int CG) {
-  const int tid = threadIdx.x;
-  const int cg = tid % CG;
-  const int roff = tid / CG;
-  const int rows_per_blk = KS_BN_BLOCK / CG;
-  const bool active = roff < rows_per_blk;
-  const long long stride = (long long)gridDim.x * rows_per_blk;
+  const NhwcRows<KS_BN_BLOCK> rows(CG);
+  const int cg = rows.cg;
+  const long long stride = rows.stride;
   const float invM = 1.f / (float)M;
   float8 mu, is, sc, bf, w, db, ds;
 #pragma unroll
@@ -651,37 +553,7 @@ __global__ void bn_bwd_apply_noy_kernel(const ushort8* __restrict__ x,
     db[j] = dbias[c] * invM;
     ds[j] = dscale[c] * invM;
   }
-  long long row = active ? (long long)blockIdx.x * rows_per_blk + roff : M;
-  for (; row + (KS_BN_UNROLL - 1) * stride < M;
-       row += KS_BN_UNROLL * stride) {
-    ushort8 xv[KS_BN_UNROLL], gv[KS_BN_UNROLL];
-    long long k[KS_BN_UNROLL];
-#pragma unroll
-    for (int u = 0; u < KS_BN_UNROLL; u++) {
-      k[u] = (row + u * stride) * CG + cg;
-      xv[u] = x[k[u]];
-      gv[u] = dy[k[u]];
-    }
-#pragma unroll
-    for (int u = 0; u < KS_BN_UNROLL; u++) {
-      ushort8 o;
-#pragma unroll
-      for (int j = 0; j < 8; j++) {
-        float xf = bf16_to_f32(xv[u][j]);
-        float g = bf16_to_f32(gv[u][j]);
-        if (RELU) {
-          float f = fmaf(xf, sc[j], bf[j]);
-          if (!f32_to_bf16(f > 0.f ? f : 0.f)) g = 0.f;
-        }
-        float xhat = (xf - mu[j]) * is[j];
-        o[j] = f32_to_bf16(w[j] * (g - db[j] - xhat * ds[j]));
-      }
-      dx[k[u]] = o;
-    }
-  }
-  for (; row < M; row += stride) {
-    const long long k = row * CG + cg;
-    ushort8 xv = x[k], gv = dy[k];
+  auto one = [&](const ushort8& xv, const ushort8& gv) {
     ushort8 o;
 #pragma unroll
     for (int j = 0; j < 8; j++) {
@@ -694,7 +566,26 @@ __global__ void bn_bwd_apply_noy_kernel(const ushort8* __restrict__ x,
       float xhat = (xf - mu[j]) * is[j];
       o[j] = f32_to_bf16(w[j] * (g - db[j] - xhat * ds[j]));
     }
-    dx[k] = o;
+    return o;
+  };
+  long long row = rows.first(M);
+  for (; row + (KS_BN_UNROLL - 1) * stride < M;
+       row += KS_BN_UNROLL * stride) {
+    ushort8 xv[KS_BN_UNROLL], gv[KS_BN_UNROLL];
+    long long k[KS_BN_UNROLL];
+#pragma unroll
+    for (int u = 0; u < KS_BN_UNROLL; u++) {
+      k[u] = (row + u * stride) * CG + cg;
+      xv[u] = x[k[u]];
+      gv[u] = dy[k[u]];
+    }
+#pragma unroll
+    for (int u = 0; u < KS_BN_UNROLL; u++) dx[k[u]] = one(xv[u], gv[u]);
+  }
+  for (; row < M; row += stride) {
+    const long long k = row * CG + cg;
+    ushort8 xv = x[k], gv = dy[k];
+    dx[k] = one(xv, gv);
   }
 }
 
@@ -710,12 +601,9 @@ __global__ void bn_bwd_apply_dym_kernel(const ushort8* __restrict__ x,
                                         const float* __restrict__ dbias,
                                         const float* __restrict__ dscale,
                                         long long M, int CG) {
-  const int tid = threadIdx.x;
-  const int cg = tid % CG;
-  const int roff = tid / CG;
-  const int rows_per_blk = KS_BN_BLOCK / CG;
-  const bool active = roff < rows_per_blk;
-  const long long stride = (long long)gridDim.x * rows_per_blk;
+  const NhwcRows<KS_BN_BLOCK> rows(CG);
+  const int cg = rows.cg;
+  const long long stride = rows.stride;
   const float invM = 1.f / (float)M;
   float8 mu, is, w, db, ds;
 #pragma unroll
@@ -727,7 +615,18 @@ __global__ void bn_bwd_apply_dym_kernel(const ushort8* __restrict__ x,
     db[j] = dbias[c] * invM;
     ds[j] = dscale[c] * invM;
   }
-  long long row = active ? (long long)blockIdx.x * rows_per_blk + roff : M;
+  // dx = w*invstd * (dym - dbias/M - xhat * dscale/M)
+  auto one = [&](const ushort8& xv, const ushort8& gv) {
+    ushort8 o;
+#pragma unroll
+    for (int j = 0; j < 8; j++) {
+      float g = bf16_to_f32(gv[j]);  // already ReLU-masked
+      float xhat = (bf16_to_f32(xv[j]) - mu[j]) * is[j];
+      o[j] = f32_to_bf16(w[j] * (g - db[j] - xhat * ds[j]));
+    }
+    return o;
+  };
+  long long row = rows.first(M);
   for (; row + (KS_BN_UNROLL - 1) * stride < M;
        row += KS_BN_UNROLL * stride) {
     ushort8 xv[KS_BN_UNROLL], gv[KS_BN_UNROLL];
@@ -739,95 +638,12 @@ __global__ void bn_bwd_apply_dym_kernel(const ushort8* __restrict__ x,
       gv[u] = dym[k[u]];
     }
 #pragma unroll
-    for (int u = 0; u < KS_BN_UNROLL; u++) {
-      ushort8 o;
-#pragma unroll
-      for (int j = 0; j < 8; j++) {
-        float g = bf16_to_f32(gv[u][j]);  // already ReLU-masked
-        float xhat = (bf16_to_f32(xv[u][j]) - mu[j]) * is[j];
-        o[j] = f32_to_bf16(w[j] * (g - db[j] - xhat * ds[j]));
-      }
-      dx[k[u]] = o;
-    }
+    for (int u = 0; u < KS_BN_UNROLL; u++) dx[k[u]] = one(xv[u], gv[u]);
   }
   for (; row < M; row += stride) {
     const long long k = row * CG + cg;
     ushort8 xv = x[k], gv = dym[k];
-    ushort8 o;
-#pragma unroll
-    for (int j = 0; j < 8; j++) {
-      float g = bf16_to_f32(gv[j]);
-      float xhat = (bf16_to_f32(xv[j]) - mu[j]) * is[j];
-      o[j] = f32_to_bf16(w[j] * (g - db[j] - xhat * ds[j]));
-    }
-    dx[k] = o;
-  }
-}
-
-// --------------------------------------------------------- bwd apply
-// dx = w*invstd * (dym - dbias/M - xhat * dscale/M)
-__global__ void bn_bwd_apply_kernel(const ushort8* __restrict__ x,
-                                    const ushort8* __restrict__ y,
-                                    const ushort8* __restrict__ dy,
-                                    ushort8* __restrict__ dx,
-                                    const float* __restrict__ mean,
-                                    const float* __restrict__ invstd,
-                                    const float* __restrict__ weight,
-                                    const float* __restrict__ dbias,
-                                    const float* __restrict__ dscale,
-                                    long long M, int CG) {
-  const int tid = threadIdx.x;
-  const int cg = tid % CG;
-  const int roff = tid / CG;
-  const int rows_per_blk = KS_BN_BLOCK / CG;
-  const bool active = roff < rows_per_blk;  // see bn_stats_kernel
-  const long long stride = (long long)gridDim.x * rows_per_blk;
-  const float invM = 1.f / (float)M;
-  float8 mu, is, w, db, ds;
-#pragma unroll
-  for (int j = 0; j < 8; j++) {
-    const int c = cg * 8 + j;
-    mu[j] = mean[c];
-    is[j] = invstd[c];
-    w[j] = weight[c] * is[j];
-    db[j] = dbias[c] * invM;
-    ds[j] = dscale[c] * invM;
-  }
-  long long row = active ? (long long)blockIdx.x * rows_per_blk + roff : M;
-  for (; row + (KS_BN_UNROLL - 1) * stride < M;
-       row += KS_BN_UNROLL * stride) {
-    ushort8 xv[KS_BN_UNROLL], yv[KS_BN_UNROLL], gv[KS_BN_UNROLL];
-    long long k[KS_BN_UNROLL];
-#pragma unroll
-    for (int u = 0; u < KS_BN_UNROLL; u++) {
-      k[u] = (row + u * stride) * CG + cg;
-      xv[u] = x[k[u]];
-      yv[u] = y[k[u]];
-      gv[u] = dy[k[u]];
-    }
-#pragma unroll
-    for (int u = 0; u < KS_BN_UNROLL; u++) {
-      ushort8 o;
-#pragma unroll
-      for (int j = 0; j < 8; j++) {
-        float g = bf16_to_f32(yv[u][j]) > 0.f ? bf16_to_f32(gv[u][j]) : 0.f;
-        float xhat = (bf16_to_f32(xv[u][j]) - mu[j]) * is[j];
-        o[j] = f32_to_bf16(w[j] * (g - db[j] - xhat * ds[j]));
-      }
-      dx[k[u]] = o;
-    }
-  }
-  for (; row < M; row += stride) {
-    const long long k = row * CG + cg;
-    ushort8 xv = x[k], yv = y[k], gv = dy[k];
-    ushort8 o;
-#pragma unroll
-    for (int j = 0; j < 8; j++) {
-      float g = bf16_to_f32(yv[j]) > 0.f ? bf16_to_f32(gv[j]) : 0.f;
-      float xhat = (bf16_to_f32(xv[j]) - mu[j]) * is[j];
-      o[j] = f32_to_bf16(w[j] * (g - db[j] - xhat * ds[j]));
-    }
-    dx[k] = o;
+    dx[k] = one(xv, gv);
   }
 }
 
@@ -887,7 +703,7 @@ void bn_launch_fwd_stats(const torch::Tensor& x, const BnGeom& g,
   auto part = at::empty({(long long)2 * g.stat_blocks * g.C}, f32);
   hipLaunchKernelGGL(bn_stats_kernel, dim3(g.stat_blocks),
                      dim3(KS_BN_BLOCK), 0, stream,
-                     reinterpret_cast<const ushort8*>(x.data_ptr()),
+                     nhwc_cptr(x),
                      part.data_ptr<float>(), g.M, g.CG);
   if (legacy_reduce) {
     auto sums = at::empty({2 * g.C}, f32);
@@ -985,11 +801,11 @@ std::vector<torch::Tensor> bn_relu_fwd_train(
   auto launch_apply = [&](auto kern) {
     hipLaunchKernelGGL(kern, dim3(g.blocks), dim3(KS_BN_BLOCK), 0,
                        stream.stream(),
-                       reinterpret_cast<const ushort8*>(x.data_ptr()),
+                       nhwc_cptr(x),
                        res.has_value()
-                           ? reinterpret_cast<const ushort8*>(res->data_ptr())
+                           ? nhwc_cptr(*res)
                            : nullptr,
-                       reinterpret_cast<ushort8*>(y.data_ptr()),
+                       nhwc_mptr(y),
                        want_mask ? mask.data_ptr<unsigned char>() : nullptr,
                        scale.data_ptr<float>(), biasf.data_ptr<float>(), g.M,
                        g.CG);
@@ -1021,11 +837,11 @@ torch::Tensor bn_relu_fwd_eval(torch::Tensor x, torch::Tensor weight,
   auto launch_apply = [&](auto kern) {
     hipLaunchKernelGGL(kern, dim3(g.blocks), dim3(KS_BN_BLOCK), 0,
                        stream.stream(),
-                       reinterpret_cast<const ushort8*>(x.data_ptr()),
+                       nhwc_cptr(x),
                        res.has_value()
-                           ? reinterpret_cast<const ushort8*>(res->data_ptr())
+                           ? nhwc_cptr(*res)
                            : nullptr,
-                       reinterpret_cast<ushort8*>(y.data_ptr()),
+                       nhwc_mptr(y),
                        (unsigned char*)nullptr, scale.data_ptr<float>(),
                        biasf.data_ptr<float>(), g.M, g.CG);
   };
@@ -1096,16 +912,14 @@ std::vector<torch::Tensor> bn_relu_bwd(
     auto launch_rstats = [&](auto kern) {
       hipLaunchKernelGGL(kern, dim3(g.stat_blocks), dim3(KS_BN_BLOCK), 0,
                          stream.stream(),
-                         reinterpret_cast<const ushort8*>(x.data_ptr()),
+                         nhwc_cptr(x),
                          use_mask ? nullptr
-                                  : reinterpret_cast<const ushort8*>(
-                                        y->data_ptr()),
+                                  : nhwc_cptr(*y),
                          use_mask ? mask->data_ptr<unsigned char>() : nullptr,
-                         reinterpret_cast<const ushort8*>(dy.data_ptr()),
-                         fold_dy2 ? reinterpret_cast<const ushort8*>(
-                                        dy2->data_ptr())
+                         nhwc_cptr(dy),
+                         fold_dy2 ? nhwc_cptr(*dy2)
                                   : nullptr,
-                         reinterpret_cast<ushort8*>(dres.data_ptr()),
+                         nhwc_mptr(dres),
                          mean.data_ptr<float>(), invstd.data_ptr<float>(),
                          part.data_ptr<float>(), g.M, g.CG);
     };
@@ -1118,9 +932,9 @@ std::vector<torch::Tensor> bn_relu_bwd(
     launch_reduce();
     hipLaunchKernelGGL(bn_bwd_apply_dym_kernel, dim3(g.blocks),
                        dim3(KS_BN_BLOCK), 0, stream.stream(),
-                       reinterpret_cast<const ushort8*>(x.data_ptr()),
-                       reinterpret_cast<const ushort8*>(dres.data_ptr()),
-                       reinterpret_cast<ushort8*>(dx.data_ptr()),
+                       nhwc_cptr(x),
+                       nhwc_cptr(dres),
+                       nhwc_mptr(dx),
                        mean.data_ptr<float>(), invstd.data_ptr<float>(),
                        weight.data_ptr<float>(), dbias_p, dscale_p,
                        g.M, g.CG);
@@ -1133,8 +947,8 @@ std::vector<torch::Tensor> bn_relu_bwd(
   auto launch_stats = [&](auto kern) {
     hipLaunchKernelGGL(kern, dim3(g.stat_blocks), dim3(KS_BN_BLOCK), 0,
                        stream.stream(),
-                       reinterpret_cast<const ushort8*>(x.data_ptr()),
-                       reinterpret_cast<const ushort8*>(dy.data_ptr()),
+                       nhwc_cptr(x),
+                       nhwc_cptr(dy),
                        mean.data_ptr<float>(), invstd.data_ptr<float>(),
                        weight.data_ptr<float>(), bias.data_ptr<float>(),
                        part.data_ptr<float>(), g.M, g.CG);
@@ -1145,9 +959,9 @@ std::vector<torch::Tensor> bn_relu_bwd(
   auto launch_bapply = [&](auto kern) {
     hipLaunchKernelGGL(kern, dim3(g.blocks), dim3(KS_BN_BLOCK), 0,
                        stream.stream(),
-                       reinterpret_cast<const ushort8*>(x.data_ptr()),
-                       reinterpret_cast<const ushort8*>(dy.data_ptr()),
-                       reinterpret_cast<ushort8*>(dx.data_ptr()),
+                       nhwc_cptr(x),
+                       nhwc_cptr(dy),
+                       nhwc_mptr(dx),
                        mean.data_ptr<float>(), invstd.data_ptr<float>(),
                        weight.data_ptr<float>(), bias.data_ptr<float>(),
                        dbias_p, dscale_p, g.M, g.CG);
