@@ -77,8 +77,9 @@ int main(int argc, char** argv) {
   BusySampler sampler;
   if (gpu_index >= 0) {
     if (sampler.init(gpu_index)) {
-      logf(g_log, "gpu-schd", "busy sampler on (gpu %d): leases charged "
-           "sampled GPU-busy, not wall", gpu_index);
+      logf(g_log, "gpu-schd", "busy sampler on (gpu %d, %s): leases charged "
+           "sampled GPU-busy, not wall", gpu_index,
+           sampler.accumulating() ? "activity counter" : "busy percent");
     } else {
       logf(g_log, "gpu-schd", "busy sampler unavailable (gpu %d): "
            "falling back to wall/RET accounting", gpu_index);

@@ -3,8 +3,10 @@
 // caps, decay, revocation and gang co-granting are tested without a
 // single sleep). Run by tests/test_native_daemons.py::test_sched_unit.
 #include <cassert>
+#include <cmath>
 #include <cstdio>
 
+#include "busy_sampler.hpp"
 #include "token_sched.hpp"
 
 using namespace ks;
@@ -508,6 +510,47 @@ int main() {
     CHECK(s.check_revoke(100000.0));
     CHECK(s.stats_json(100000.0).find("\"last_revoked\":\"ns/evil\\\"") !=
           std::string::npos);
+  }
+
+  // ---- 23. busy ms from the low-passed, integer busy percent: a
+  // 30 %-duty pod (90 ms bursts, 210 ms gaps) whose lease ends 30 ms
+  // after each burst is charged its bursts, although most of the
+  // percent reading's area trails behind the lease
+  {
+    BusyPercentIntegrator from_pct;
+    from_pct.reset(0.0);
+    // the simulated SMU's time constant is the measured one, not the
+    // class's: profiles/busy_counter_calibration.txt, a step to 100 %
+    // busy read at 20 ms spacing gives 18, 33, 45, 55, 63 =
+    // 100 * (1 - exp(-t / 100))
+    const double decay = std::exp(-1.0 / 100.0);
+    for (int k = 1; k <= 5; k++) {
+      const double measured[] = {18, 33, 45, 55, 63};
+      CHECK(std::fabs(100.0 * (1.0 - std::pow(decay, 20.0 * k)) -
+                      measured[k - 1]) < 1.0);
+    }
+    double y = 0.0;                      // the SMU's filtered activity
+    double in_lease = 0.0, outside = 0.0, naive_in_lease = 0.0;
+    for (int ms = 1; ms <= 3000; ms++) {
+      int phase = (ms - 1) % 300;
+      y = (phase < 90 ? 100.0 : 0.0) * (1.0 - decay) + y * decay;
+      if (ms % 5) continue;              // gpu-schd's 5 ms tick
+      double pct = std::floor(y);
+      double busy = from_pct.step(pct, 5.0);
+      CHECK(busy >= 0.0 && busy <= 5.0);
+      bool held = phase < 120;
+      (held ? in_lease : outside) += busy;
+      if (held) naive_in_lease += pct / 100.0 * 5.0;
+    }
+    CHECK(std::fabs(in_lease - 900.0) < 0.03 * 900.0);
+    CHECK(outside < 0.03 * 900.0);
+    CHECK(naive_in_lease < 0.6 * 900.0);  // what summing pct*dt would charge
+    // a saturated GPU is all busy, an idle one stays at zero
+    double full = 0.0;
+    for (int i = 0; i < 100; i++) full += from_pct.step(100.0, 5.0);
+    CHECK(full > 495.0 && full <= 500.0);
+    from_pct.reset(0.0);
+    CHECK(from_pct.step(0.0, 200.0) == 0.0);
   }
 
   printf("sched_test OK (%d checks)\n", g_checks);

@@ -6,7 +6,9 @@ Runs three 2-second phases — idle, 100% busy (ks_ops.burn), ~30% duty
 bursts — and for each prints the instantaneous busy_percent samples and
 the coarse-grain accumulated counter delta (expected: delta/100 =
 busy_ms; rocm_smi.h: "every millisecond the firmware calculates % busy
-and accumulates it").
+and accumulates it"). A last phase polls both readings every ms under
+the bursts and prints how often the counter refreshes and how the busy
+percent rises and decays.
 
     gpurun -- 'python tools/busy_probe.py > gpurun_out/busy_probe.txt'
 """
@@ -78,6 +80,45 @@ def main():
         t.cuda.synchronize()
         time.sleep(0.070)
     phase("bursty30", bursty)
+    refresh(read_acc, read_pct, bursty, t)
+
+
+def refresh(read_acc, read_pct, load, t, seconds=3.0):
+    """How often each reading changes under the bursty load, polled every
+    ms from a second thread: the accumulated counter's refresh interval
+    (1 ms on bare metal, 1 s on a virtual function) and the busy percent
+    over the first bursts, which shows the SMU's smoothing (tau)."""
+    import threading
+    acc, pct, stop = [], [], threading.Event()
+
+    def poll():
+        t0 = time.perf_counter()
+        last = None
+        while not stop.is_set():
+            _, a, ts = read_acc()
+            _, p = read_pct()
+            now = (time.perf_counter() - t0) * 1000
+            if (a, ts) != last:
+                acc.append((now, a, ts))
+                last = (a, ts)
+            pct.append((now, p))
+            time.sleep(0.001)
+
+    th = threading.Thread(target=poll)
+    th.start()
+    end = time.perf_counter() + seconds
+    while time.perf_counter() < end:
+        load()
+    t.cuda.synchronize()
+    stop.set()
+    th.join()
+    steps = [(round(b[0] - a[0]), b[1] - a[1], round((b[2] - a[2]) / 1e6))
+             for a, b in zip(acc[1:], acc[2:])]
+    print(f"refresh: polls={len(pct)} acc_changes={len(acc) - 1} "
+          f"(dt_ms, acc_delta, ts_delta_ms)={steps[:5]}...")
+    series = [(round(now), p) for now, p in pct if now <= 210.0][::5]
+    print(f"refresh: (t_ms, pct) over 30 ms busy / 70 ms idle = {series}",
+          flush=True)
 
 
 if __name__ == "__main__":
