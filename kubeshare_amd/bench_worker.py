@@ -93,6 +93,13 @@ def main():
                     help="use the kubeshare_amd HIP fused ops")
     ap.add_argument("--fused-sgd", action="store_true",
                     help="use the HIP multi-tensor SGD instead of torch's")
+    ap.add_argument("--clip-grad-norm", type=float, default=None,
+                    metavar="F",
+                    help="clip the gradient to global L2 norm F inside the "
+                         "fused SGD step (needs --fused-sgd)")
+    ap.add_argument("--lars", type=float, default=None, metavar="ETA",
+                    help="layer-wise trust ratio with coefficient ETA in "
+                         "the fused SGD step (needs --fused-sgd)")
     ap.add_argument("--miopen-find", action=argparse.BooleanOptionalAction,
                     default=True,
                     help="benchmark every MIOpen solver per conv shape at "
@@ -103,6 +110,10 @@ def main():
                          "as DIR/<dump-name>.*.npy and print DUMPED")
     ap.add_argument("--dump-name", default="pod")
     args = ap.parse_args()
+    if (args.clip_grad_norm is not None or args.lars is not None) \
+            and not args.fused_sgd:
+        ap.error("--clip-grad-norm and --lars need --fused-sgd: only the "
+                 "fused step has the norm kernels")
 
     from kubeshare_amd.utils.tuning import apply_miopen_tuning
     apply_miopen_tuning()  # before the first conv
@@ -141,7 +152,12 @@ def main():
     if use_ops and args.fused_sgd:
         from kubeshare_amd import ops as _ops
         opt = _ops.FusedSGD(model.parameters(), lr=args.lr, momentum=0.9,
-                            weight_decay=1e-4)
+                            weight_decay=1e-4,
+                            max_grad_norm=args.clip_grad_norm,
+                            lars=args.lars)
+    elif args.clip_grad_norm is not None or args.lars is not None:
+        raise SystemExit("--clip-grad-norm and --lars need the fused ops "
+                         "(a GPU and --use-ops auto or on)")
     else:
         opt = torch.optim.SGD(model.parameters(), lr=args.lr, momentum=0.9,
                               weight_decay=1e-4)

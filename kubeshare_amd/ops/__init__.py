@@ -20,7 +20,8 @@ _SRCS = [os.path.join(_HERE, "hip", "ks_ops.hip"),
          os.path.join(_HERE, "hip", "bias_relu.hip"),
          os.path.join(_HERE, "hip", "cast.hip"),
          os.path.join(_HERE, "hip", "conv_split.hip"),
-         os.path.join(_HERE, "hip", "grad_bucket.hip")]
+         os.path.join(_HERE, "hip", "grad_bucket.hip"),
+         os.path.join(_HERE, "hip", "grad_norm.hip")]
 
 _ext = None
 
@@ -110,13 +111,46 @@ class FusedSGD:
     every rank must all-reduce the same layout, and a rank that raised
     or skipped would leave its peers waiting. With process_group=None
     nothing of this exists and the optimizer is the ungrouped one.
+
+    max_grad_norm clips the gradient by its global L2 norm, as
+    torch.nn.utils.clip_grad_norm_ does: g is used as c*g with
+    c = min(1, max_grad_norm / (norm + 1e-6)). lars (the trust
+    coefficient eta) turns on the layer-wise trust ratio: a tensor for
+    which lars_exclude(p) is false (default: excluded when p.ndim <= 1,
+    the BN scales and the biases) steps by
+        trust = eta*||w|| / (c*||g|| + wd*||w|| + lars_eps)
+        v = mu*v + trust * (c*g + wd*w) ;  w -= lr*v
+    (trust = 1 where ||w|| or ||g|| is 0); an excluded tensor takes the
+    clipped plain step. With either on, step() is: the multi-tensor
+    sum-of-squares kernel over the gradients (and the weights with
+    lars), one finalize kernel, the update kernel, which reads norm,
+    coefficient and trust ratios from a persistent device workspace:
+    no host sync, the gradients are never rewritten, and the step is
+    captured and replayed like the plain one (a replay recomputes the
+    norm from what the gradient buffers then hold). A step whose norm
+    is not finite changes nothing and is counted. grad_norm (0-d f32,
+    the last step's pre-clip global norm) and nonfinite_steps (0-d
+    int32) are views of that workspace: reading them does not sync.
+    Under a process_group the norm is the averaged gradient's. These
+    steps always use the multi-tensor kernels (KUBESHARE_SGD_MULTI does
+    not apply). With both arguments None nothing of this exists.
     """
 
     def __init__(self, params, lr: float, momentum: float = 0.9,
                  weight_decay: float = 0.0, graph_mode: str = "auto",
-                 process_group=None, grad_dtype=None):
+                 process_group=None, grad_dtype=None, max_grad_norm=None,
+                 lars=None, lars_eps: float = 1e-8, lars_exclude=None):
+        import math
+
         import torch
 
+        for name, val in (("max_grad_norm", max_grad_norm), ("lars", lars)):
+            if val is not None and not (math.isfinite(val) and val > 0):
+                raise ValueError(f"FusedSGD: {name} must be a finite "
+                                 f"positive number or None, not {val!r}")
+        if not (math.isfinite(lars_eps) and lars_eps >= 0):
+            raise ValueError("FusedSGD: lars_eps must be finite and >= 0, "
+                             f"not {lars_eps!r}")
         self.params = [p for p in params if p.requires_grad]
         self._bucket = None
         if process_group is not None and process_group is not False:
@@ -140,6 +174,23 @@ class FusedSGD:
         self._multi = os.environ.get("KUBESHARE_SGD_MULTI", "1") != "0"
         self._step_graph = None
         self._graph_ptrs = None  # data_ptrs the graph was baked on
+        self.max_grad_norm = max_grad_norm
+        self.lars = lars
+        self.lars_eps = lars_eps
+        self._norm_ws = None
+        if max_grad_norm is not None or lars is not None:
+            if lars_exclude is None:
+                def lars_exclude(p):
+                    return p.ndim <= 1
+            self._lars_mask = [lars is not None and not lars_exclude(p)
+                               for p in self.params]
+            self._norm_ws = torch.zeros(
+                _load().grad_norm_ws_size(
+                    [p.numel() for p in self.params], lars is not None),
+                dtype=torch.float32,
+                device=self.params[0].device if self.params else "cpu")
+            self.grad_norm = self._norm_ws[0]
+            self.nonfinite_steps = self._norm_ws[3].view(torch.int32)
 
     def _graphable(self):
         import torch
@@ -153,10 +204,13 @@ class FusedSGD:
     def _ptrs(self):
         """Every address a captured step would touch; a replay is valid
         only while all of them are what they were at capture."""
-        return tuple(
+        ptrs = tuple(
             (p.data_ptr(), v.data_ptr(),
              p.grad.data_ptr() if p.grad is not None else 0)
             for p, v in zip(self.params, self.momenta))
+        if self._norm_ws is not None:
+            ptrs += (self._norm_ws.data_ptr(),)
+        return ptrs
 
     def zero_grad(self, set_to_none: bool = True):
         for p in self.params:
@@ -165,8 +219,30 @@ class FusedSGD:
             elif p.grad is not None:
                 p.grad.zero_()
 
+    def _norm_step(self, grads):
+        """Sums of squares, finalize, update: the clipped / LARS step
+        from `grads`, which have their parameters' strides."""
+        ext = _load()
+        ps = [p.data for p in self.params]
+        ext.grad_sumsq_multi(grads, ps if self.lars is not None else [],
+                             self._norm_ws, self.max_grad_norm or 0.0, True)
+        ext.sgd_momentum_multi_norm_(
+            ps, grads, self.momenta, self.lr, self.momentum,
+            self.weight_decay, self._norm_ws, self.lars or 0.0,
+            self.lars_eps, self._lars_mask)
+
     def _launch(self):
         ext = _load()
+        if self._norm_ws is not None:
+            import torch
+
+            # a gradient with other strides than its parameter's (rare) is
+            # re-strided once, for both kernels
+            self._norm_step([
+                p.grad if p.grad is None or p.grad.stride() == p.stride()
+                else torch.empty_like(p).copy_(p.grad)
+                for p in self.params])
+            return
         if self._multi:
             ext.sgd_momentum_multi_(
                 [p.data for p in self.params],
@@ -190,6 +266,9 @@ class FusedSGD:
         bucket = self._bucket
         bucket.pack([p.grad for p in self.params], 1.0 / self._world)
         bucket.all_reduce(self._group)
+        if self._norm_ws is not None:
+            self._norm_step(bucket.views)
+            return
         ext = _load()
         sgd = ext.sgd_momentum_multi_ if bucket.dtype == torch.float32 \
             else ext.sgd_momentum_multi_bf16g_
@@ -377,6 +456,49 @@ def broadcast_parameters(model, src: int = 0, group=None):
         bucket.pack(tensors)
         dist.broadcast(bucket.flat, src=src, group=group)
         bucket.unpack(tensors)
+
+
+# ------------------------------------------------------ gradient norms
+def grad_norm(tensors, per_tensor: bool = False):
+    """The global L2 norm of a list of dense f32 or bf16 tensors on one
+    device (one dtype; None entries count as zero) as a 0-d f32 tensor;
+    with per_tensor the pair (global norm, f32 vector of per-tensor
+    norms). On CUDA tensors it runs hip/grad_norm.hip's two
+    deterministic kernels and nothing else (at most 1000 tensors): no
+    atomics, so two calls return the same bits. On CPU tensors it runs
+    the plain torch expression, so the argument handling is testable
+    without a GPU."""
+    import torch
+
+    tensors = list(tensors)
+    some = [t for t in tensors if t is not None]
+    for t in some:
+        if t.dtype != some[0].dtype or t.dtype not in (torch.float32,
+                                                       torch.bfloat16):
+            raise ValueError("grad_norm: f32 or bf16 tensors of one dtype "
+                             "expected")
+        if t.device != some[0].device:
+            raise ValueError("grad_norm: tensors on one device expected")
+        if not _dense(t):
+            raise ValueError("grad_norm: tensors must be non-overlapping "
+                             "and dense")
+    if some and some[0].is_cuda:
+        ext = _load()
+        T = len(tensors)
+        with torch.cuda.device(some[0].device):
+            ws = torch.empty(
+                ext.grad_norm_ws_size(
+                    [0 if t is None else t.numel() for t in tensors], False),
+                dtype=torch.float32, device=some[0].device)
+            ext.grad_sumsq_multi(tensors, [], ws, 0.0, False)
+        total, each = ws[0], ws[4 + 2 * T:4 + 3 * T]
+    else:
+        each = torch.stack([
+            torch.zeros(()) if t is None
+            else torch.linalg.vector_norm(t.detach().float())
+            for t in tensors]) if tensors else torch.zeros(0)
+        total = torch.linalg.vector_norm(each)
+    return (total, each) if per_tensor else total
 
 
 # ---------------------------------------------- shared NHWC predicates

@@ -15,6 +15,9 @@
 //    launch; pointers and block prefix sums ride in the kernel arguments
 //    (ResNet50's 161 tensors: 2 launches instead of 161). Templated on
 //    the gradient type: f32, or bf16 from a bf16 gradient bucket.
+//  - sgd_mom_multi_norm_f32_kernel: that kernel's body with global-norm
+//    clipping and the LARS trust ratio applied in registers, read from
+//    the device workspace that grad_norm.hip fills (bound below).
 //  - grad_bucket.hip: multi-tensor pack / unpack between per-parameter
 //    gradients and the flat bucket a gang all-reduces (bound below).
 //  - bn_relu.hip / pool.hip / cast.hip: fused NHWC bf16 BN+ReLU(+add),
@@ -31,6 +34,8 @@
 
 #include <type_traits>
 #include <vector>
+
+#include "grad_norm.h"
 
 #define WAVE 64
 
@@ -95,6 +100,46 @@ __device__ __forceinline__ void sgd_mom_update4(float4& p, const float4& g,
   sgd_mom_update(p.w, g.w, v.w, lr, mu, wd);
 }
 
+// The clipped / LARS update, also spelled once and with explicit FMAs
+// for the reason above. c is the clip coefficient: with c == 1 the
+// product c*g is g and the clip-only branch is sgd_mom_update bit for
+// bit. A LARS tensor scales the whole step, weight decay included, by
+// its trust ratio.
+struct SgdRule {
+  float lr, mu, wd;
+  float c, trust;
+  bool lars;
+};
+
+__device__ __forceinline__ void sgd_mom_update_norm(float& p, float g,
+                                                    float& v,
+                                                    const SgdRule& r) {
+  const float cg = r.c * g;
+  if (r.lars)
+    v = fmaf(r.mu, v, r.trust * fmaf(r.wd, p, cg));
+  else
+    v = fmaf(r.wd, p, fmaf(r.mu, v, cg));
+  p = fmaf(-r.lr, v, p);
+}
+
+template <bool NORM>
+__device__ __forceinline__ void sgd_apply(float& p, float g, float& v,
+                                          const SgdRule& r) {
+  if (NORM)
+    sgd_mom_update_norm(p, g, v, r);
+  else
+    sgd_mom_update(p, g, v, r.lr, r.mu, r.wd);
+}
+
+template <bool NORM>
+__device__ __forceinline__ void sgd_apply4(float4& p, const float4& g,
+                                           float4& v, const SgdRule& r) {
+  sgd_apply<NORM>(p.x, g.x, v.x, r);
+  sgd_apply<NORM>(p.y, g.y, v.y, r);
+  sgd_apply<NORM>(p.z, g.z, v.z, r);
+  sgd_apply<NORM>(p.w, g.w, v.w, r);
+}
+
 __global__ void sgd_mom_f32_kernel(float* __restrict__ p,
                                    const float* __restrict__ g,
                                    float* __restrict__ v, float lr, float mu,
@@ -144,10 +189,29 @@ struct SgdMultiArgs {
   int blk[KS_SGD_MAX_TENSORS + 1];
   int count;
   float lr, mu, wd;
+  using grad_t = G;
+  static constexpr bool kNorm = false;
 };
 static_assert(sizeof(SgdMultiArgs<float>) <= 4096 &&
                   sizeof(SgdMultiArgs<unsigned short>) <= 4096,
               "SgdMultiArgs must fit the 4 KiB kernel-argument segment");
+
+// The clipping / LARS instantiation's arguments. Slot i of a launch is
+// tensor first + i of the optimizer's list, which is its index in the
+// norm workspace (grad_norm.h), so here a tensor without a gradient keeps
+// its slot and owns no block. Bit i of lars says whether slot i takes the
+// trust ratio (one bit per tensor: a byte each would not fit).
+template <typename G>
+struct SgdNormArgs : SgdMultiArgs<G> {
+  const float* ws;  // norm workspace of T tensors
+  float eta, eps;
+  int first, T;
+  unsigned int lars[(KS_SGD_MAX_TENSORS + 31) / 32];
+  static constexpr bool kNorm = true;
+};
+static_assert(sizeof(SgdNormArgs<float>) <= 4096 &&
+                  sizeof(SgdNormArgs<unsigned short>) <= 4096,
+              "SgdNormArgs must fit the 4 KiB kernel-argument segment");
 
 // four / one gradient element(s) as f32 (bf16 -> f32 is exact)
 __device__ __forceinline__ float4 sgd_load_g4(const float* g, int k) {
@@ -168,12 +232,14 @@ __device__ __forceinline__ float sgd_load_g(const unsigned short* g, int k) {
   return __uint_as_float((unsigned int)g[k] << 16);
 }
 
-template <typename G>
-__global__ void __launch_bounds__(KS_SGD_THREADS)
-sgd_mom_multi_f32_kernel(const SgdMultiArgs<G> a) {
+template <typename A>
+__device__ __forceinline__ void sgd_mom_multi_body(const A& a) {
+  using G = typename A::grad_t;
+  constexpr bool NORM = A::kNorm;
   const int b = blockIdx.x;
   // largest t with blk[t] <= b (blk is non-decreasing, blk[0] == 0,
-  // b < blk[count]; tensors own >= 1 block, so the answer is unique)
+  // b < blk[count]; tensors own >= 1 block, so the answer is unique;
+  // SgdNormArgs' slots without a block are never it: blk[lo + 1] > b)
   int lo = 0, hi = a.count - 1;
   while (lo < hi) {
     int mid = (lo + hi + 1) >> 1;
@@ -183,7 +249,22 @@ sgd_mom_multi_f32_kernel(const SgdMultiArgs<G> a) {
   const G* __restrict__ g = a.g[lo];
   float* __restrict__ v = a.v[lo];
   const long long n = a.n[lo];
-  const float lr = a.lr, mu = a.mu, wd = a.wd;
+  SgdRule r = {a.lr, a.mu, a.wd, 1.0f, 1.0f, false};
+  if constexpr (NORM) {
+    // once per block: skip the step on a non-finite norm, else the clip
+    // coefficient and, for a LARS tensor, its trust ratio
+    const float* ws = a.ws;
+    if (ws[KS_NORM_WS_FINITE] == 0.0f) return;
+    r.c = ws[KS_NORM_WS_COEF];
+    if ((a.lars[lo >> 5] >> (lo & 31)) & 1) {
+      const int t = a.first + lo;
+      const float wn = sqrtf(ws[KS_NORM_WS_HEAD + a.T + t]);
+      const float gn = r.c * sqrtf(ws[KS_NORM_WS_HEAD + t]);
+      r.lars = true;
+      if (wn > 0.0f && gn > 0.0f)
+        r.trust = a.eta * wn / (gn + a.wd * wn + a.eps);
+    }
+  }
   const long long base = (long long)(b - a.blk[lo]) * KS_SGD_CHUNK;
   long long rem = n - base;  // > 0 by construction of blk
   const int len = rem < KS_SGD_CHUNK ? (int)rem : KS_SGD_CHUNK;
@@ -213,7 +294,7 @@ sgd_mom_multi_f32_kernel(const SgdMultiArgs<G> a) {
 #pragma unroll
       for (int u = 0; u < KS_SGD_VPT; u++) {
         const int k = tid + u * KS_SGD_THREADS;
-        sgd_mom_update4(pv[u], gv[u], vv[u], lr, mu, wd);
+        sgd_apply4<NORM>(pv[u], gv[u], vv[u], r);
         v4[k] = vv[u];
         p4[k] = pv[u];
       }
@@ -221,13 +302,13 @@ sgd_mom_multi_f32_kernel(const SgdMultiArgs<G> a) {
     }
     for (int k = tid; k < len4; k += KS_SGD_THREADS) {
       float4 pv = p4[k], gv = sgd_load_g4(g, k), vv = v4[k];
-      sgd_mom_update4(pv, gv, vv, lr, mu, wd);
+      sgd_apply4<NORM>(pv, gv, vv, r);
       v4[k] = vv;
       p4[k] = pv;
     }
     for (int k = len4 * 4 + tid; k < len; k += KS_SGD_THREADS) {
       float pv = p[k], vv = v[k];
-      sgd_mom_update(pv, sgd_load_g(g, k), vv, lr, mu, wd);
+      sgd_apply<NORM>(pv, sgd_load_g(g, k), vv, r);
       v[k] = vv;
       p[k] = pv;
     }
@@ -235,10 +316,22 @@ sgd_mom_multi_f32_kernel(const SgdMultiArgs<G> a) {
   }
   for (int k = tid; k < len; k += KS_SGD_THREADS) {
     float pv = p[k], vv = v[k];
-    sgd_mom_update(pv, sgd_load_g(g, k), vv, lr, mu, wd);
+    sgd_apply<NORM>(pv, sgd_load_g(g, k), vv, r);
     v[k] = vv;
     p[k] = pv;
   }
+}
+
+template <typename G>
+__global__ void __launch_bounds__(KS_SGD_THREADS)
+sgd_mom_multi_f32_kernel(const SgdMultiArgs<G> a) {
+  sgd_mom_multi_body(a);
+}
+
+template <typename G>
+__global__ void KS_NO_PK_F32 __launch_bounds__(KS_SGD_THREADS)
+sgd_mom_multi_norm_f32_kernel(const SgdNormArgs<G> a) {
+  sgd_mom_multi_body(a);
 }
 
 void sgd_momentum_(std::vector<torch::Tensor> params,
@@ -273,12 +366,16 @@ void sgd_momentum_(std::vector<torch::Tensor> params,
 // tensors -> 2). grads[t] may be None: that tensor is skipped. Returns
 // the number of kernels launched. G = float: f32 gradients; G = unsigned
 // short: bf16 gradients, which must already have the parameter's strides.
-template <typename G>
+// A = SgdNormArgs<G> (a pre-filled with ws, eta, eps and T; lars[t] says
+// whether tensor t takes the trust ratio): the clipping / LARS kernel,
+// where a skipped tensor keeps its slot.
+template <typename A>
 static int64_t sgd_momentum_multi_impl(
     const std::vector<torch::Tensor>& params,
     const std::vector<c10::optional<torch::Tensor>>& grads,
     const std::vector<torch::Tensor>& momenta, double lr, double mu,
-    double wd) {
+    double wd, A a = {}, const std::vector<bool>& lars = {}) {
+  using G = typename A::grad_t;
   constexpr bool g_f32 = std::is_same<G, float>::value;
   const auto gtype = g_f32 ? at::kFloat : at::kBFloat16;
   TORCH_CHECK(params.size() == grads.size() &&
@@ -287,7 +384,6 @@ static int64_t sgd_momentum_multi_impl(
               "length");
   auto stream = at::cuda::getCurrentCUDAStream();
   const long long max_blocks = 1LL << 30;
-  SgdMultiArgs<G> a = {};
   a.lr = (float)lr;
   a.mu = (float)mu;
   a.wd = (float)wd;
@@ -298,13 +394,39 @@ static int64_t sgd_momentum_multi_impl(
   std::vector<torch::Tensor> keep;
   auto flush = [&]() {
     if (a.count == 0) return;
-    hipLaunchKernelGGL(sgd_mom_multi_f32_kernel<G>, dim3(a.blk[a.count]),
-                       dim3(KS_SGD_THREADS), 0, stream.stream(), a);
-    launches++;
+    if constexpr (A::kNorm) {
+      if (a.blk[a.count] > 0) {
+        hipLaunchKernelGGL(sgd_mom_multi_norm_f32_kernel<G>,
+                           dim3(a.blk[a.count]), dim3(KS_SGD_THREADS), 0,
+                           stream.stream(), a);
+        launches++;
+      }
+      a.first += a.count;
+      for (unsigned int& bits : a.lars) bits = 0;
+    } else {
+      hipLaunchKernelGGL(sgd_mom_multi_f32_kernel<G>, dim3(a.blk[a.count]),
+                         dim3(KS_SGD_THREADS), 0, stream.stream(), a);
+      launches++;
+    }
     a.count = 0;
   };
+  // the clipping / LARS kernel: a tensor that is skipped keeps its slot
+  auto skip = [&]() {
+    if constexpr (A::kNorm) {
+      if (a.count == KS_SGD_MAX_TENSORS) flush();
+      a.p[a.count] = nullptr;
+      a.g[a.count] = nullptr;
+      a.v[a.count] = nullptr;
+      a.n[a.count] = 0;
+      a.blk[a.count + 1] = a.blk[a.count];
+      a.count++;
+    }
+  };
   for (size_t t = 0; t < params.size(); t++) {
-    if (!grads[t].has_value() || !grads[t]->defined()) continue;
+    if (!grads[t].has_value() || !grads[t]->defined()) {
+      skip();
+      continue;
+    }
     auto& p = params[t];
     auto& v = momenta[t];
     torch::Tensor g = *grads[t];
@@ -333,11 +455,17 @@ static int64_t sgd_momentum_multi_impl(
                 "sgd_momentum_multi_: parameter, gradient and momentum "
                 "must live on the current device and share a shape");
     const long long n = p.numel();
-    if (n == 0) continue;
+    if (n == 0) {
+      skip();
+      continue;
+    }
     const long long nb = (n + KS_SGD_CHUNK - 1) / KS_SGD_CHUNK;
     TORCH_CHECK(nb <= max_blocks, "sgd_momentum_multi_: tensor too large");
     if (a.count == KS_SGD_MAX_TENSORS || a.blk[a.count] + nb > max_blocks)
       flush();
+    if constexpr (A::kNorm) {
+      if (lars[t]) a.lars[a.count >> 5] |= 1u << (a.count & 31);
+    }
     a.p[a.count] = p.data_ptr<float>();
     a.g[a.count] = static_cast<const G*>(g.data_ptr());
     a.v[a.count] = v.data_ptr<float>();
@@ -353,7 +481,8 @@ int64_t sgd_momentum_multi_(std::vector<torch::Tensor> params,
                             std::vector<c10::optional<torch::Tensor>> grads,
                             std::vector<torch::Tensor> momenta, double lr,
                             double mu, double wd) {
-  return sgd_momentum_multi_impl<float>(params, grads, momenta, lr, mu, wd);
+  return sgd_momentum_multi_impl<SgdMultiArgs<float>>(params, grads, momenta,
+                                                      lr, mu, wd);
 }
 
 // The same update from bf16 gradients of the parameters' sizes and
@@ -362,8 +491,49 @@ int64_t sgd_momentum_multi_bf16g_(
     std::vector<torch::Tensor> params,
     std::vector<c10::optional<torch::Tensor>> grads,
     std::vector<torch::Tensor> momenta, double lr, double mu, double wd) {
-  return sgd_momentum_multi_impl<unsigned short>(params, grads, momenta, lr,
-                                                 mu, wd);
+  return sgd_momentum_multi_impl<SgdMultiArgs<unsigned short>>(
+      params, grads, momenta, lr, mu, wd);
+}
+
+// The update with the clip coefficient, the finite flag and, where
+// lars[t], tensor t's trust ratio eta*||w|| / (c*||g|| + wd*||w|| + eps)
+// read from the workspace that grad_sumsq_multi filled for these tensors
+// in this order (grad_norm.h). The gradients are f32 or bf16 (decided by
+// the first one; a bf16 gradient has its parameter's strides). lars is
+// empty or one flag per tensor.
+int64_t sgd_momentum_multi_norm_(
+    std::vector<torch::Tensor> params,
+    std::vector<c10::optional<torch::Tensor>> grads,
+    std::vector<torch::Tensor> momenta, double lr, double mu, double wd,
+    torch::Tensor ws, double eta, double eps, std::vector<bool> lars) {
+  const char* name = "sgd_momentum_multi_norm_";
+  const int64_t T = (int64_t)params.size();
+  TORCH_CHECK(ws.is_cuda() && ws.dim() == 1 && ws.is_contiguous() &&
+                  ws.scalar_type() == at::kFloat &&
+                  ws.numel() >= KS_NORM_WS_HEAD + 3 * T &&
+                  ws.get_device() ==
+                      at::cuda::getCurrentCUDAStream().device_index(),
+              name, ": the workspace is a contiguous 1-D f32 tensor on the "
+              "current device with room for every tensor");
+  if (lars.empty()) lars.assign(params.size(), false);
+  TORCH_CHECK(lars.size() == params.size(), name,
+              ": one LARS flag per tensor expected");
+  bool bf16 = false;
+  for (const auto& g : grads)
+    if (g.has_value() && g->defined()) {
+      bf16 = g->scalar_type() == at::kBFloat16;
+      break;
+    }
+  auto run = [&](auto a) {
+    a.ws = ws.data_ptr<float>();
+    a.eta = (float)eta;
+    a.eps = (float)eps;
+    a.first = 0;
+    a.T = (int)T;
+    return sgd_momentum_multi_impl(params, grads, momenta, lr, mu, wd, a,
+                                   lars);
+  };
+  return bf16 ? run(SgdNormArgs<unsigned short>{}) : run(SgdNormArgs<float>{});
 }
 
 // fused NHWC bf16 BatchNorm+ReLU (bn_relu.hip)
@@ -397,6 +567,13 @@ std::vector<torch::Tensor> bn_join_bwd(
     torch::Tensor weight_d, torch::Tensor mean, torch::Tensor invstd,
     torch::Tensor mean_d, torch::Tensor invstd_d, bool use_mask,
     bool legacy_reduce);
+
+// multi-tensor sums of squares, global norm, clip coefficient
+// (grad_norm.hip)
+int64_t grad_sumsq_multi(std::vector<c10::optional<torch::Tensor>> grads,
+                         std::vector<c10::optional<torch::Tensor>> weights,
+                         torch::Tensor ws, double max_norm, bool tally);
+int64_t grad_norm_ws_size(std::vector<int64_t> numels, bool lars);
 
 // flat gradient bucket pack / unpack (grad_bucket.hip)
 int64_t grad_pack_multi(std::vector<c10::optional<torch::Tensor>> srcs,
@@ -471,6 +648,22 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("sgd_momentum_multi_bf16g_", &sgd_momentum_multi_bf16g_,
         "sgd_momentum_multi_ reading bf16 gradients that have the "
         "parameters' sizes and strides");
+  m.def("sgd_momentum_multi_norm_", &sgd_momentum_multi_norm_,
+        py::arg("params"), py::arg("grads"), py::arg("momenta"),
+        py::arg("lr"), py::arg("mu"), py::arg("wd"), py::arg("ws"),
+        py::arg("eta"), py::arg("eps"), py::arg("lars"),
+        "sgd_momentum_multi_ with the clip coefficient, the finite flag "
+        "and, where lars[t], the trust ratio read from the norm workspace "
+        "ws on the device; f32 or bf16 gradients");
+  m.def("grad_sumsq_multi", &grad_sumsq_multi, py::arg("grads"),
+        py::arg("weights"), py::arg("ws"), py::arg("max_norm"),
+        py::arg("tally"),
+        "per-tensor sums of squares of grads (and of weights unless "
+        "empty), global norm, clip coefficient and finite flag into the "
+        "workspace ws, by two deterministic kernels; returns the number "
+        "of launches");
+  m.def("grad_norm_ws_size", &grad_norm_ws_size, py::arg("numels"),
+        py::arg("lars"), "f32 elements of a norm workspace");
   m.def("grad_pack_multi", &grad_pack_multi, py::arg("srcs"),
         py::arg("flat"), py::arg("offsets"), py::arg("scale"),
         py::arg("like"),

@@ -75,7 +75,7 @@ def _check_replicas(model):
 def ddp_worker(model_name: str = "resnet18", batch: int = 32,
                image_size: int = 224, steps: int = 10,
                warmup: int = 3, fused: bool = False,
-               grad_dtype="f32") -> float:
+               grad_dtype="f32", max_grad_norm=None, lars=None) -> float:
     """One DDP rank: init from the torchrun/env contract, train
     `steps` timed steps, return ms/step (rank 0 also prints a
     DDP_RESULT line).
@@ -87,13 +87,17 @@ def ddp_worker(model_name: str = "resnet18", batch: int = 32,
     gradients with one all-reduce of a flat bucket per step ("f32" or
     "bf16" on the wire). After the timed steps the ranks compare a
     checksum of their parameters and raise if they differ. Needs a
-    GPU."""
+    GPU. max_grad_norm / lars are ops.FusedSGD's (clipping by the
+    averaged gradient's global norm, layer-wise trust ratio) and need
+    fused=True."""
     import torch
     import torch.distributed as dist
 
     from ..models import build_model
 
     on_gpu = torch.cuda.is_available()
+    if (max_grad_norm is not None or lars is not None) and not fused:
+        raise ValueError("max_grad_norm and lars need fused=True")
     if fused and not on_gpu:
         raise RuntimeError("ddp_worker(fused=True) needs a GPU: the fused "
                            "path has no CPU kernels")
@@ -117,7 +121,8 @@ def ddp_worker(model_name: str = "resnet18", batch: int = 32,
         ops.broadcast_parameters(model, src=0)
         opt = ops.FusedSGD(model.parameters(), lr=0.01, momentum=0.9,
                            process_group=True,
-                           grad_dtype=_grad_dtype(grad_dtype))
+                           grad_dtype=_grad_dtype(grad_dtype),
+                           max_grad_norm=max_grad_norm, lars=lars)
     else:
         model = build_model(model_name).to(dev)
         if on_gpu:
@@ -152,15 +157,20 @@ def launch_gang(ranks: int = 2, share_gpu: bool = False, steps: int = 10,
                 model: str = "resnet18", batch: int = 32,
                 image_size: int = 224, timeout: float = 300.0,
                 master_port: int = 29571, fused: bool = False,
-                grad_dtype: str = "f32"):
+                grad_dtype: str = "f32", max_grad_norm=None, lars=None):
     """Run a DDP gang under the full isolation chain. Returns
     (all_ok, per_gpu_stats) where per_gpu_stats is each
     LocalGPUShare's final gpu-schd STATS dict (server-side quota
     accounting, keyed by pod). fused / grad_dtype ("f32" or "bf16")
     are ddp_worker's: the gang trains on the fused path, and a gang
-    whose replicas diverged reports not ok."""
+    whose replicas diverged reports not ok. max_grad_norm / lars are
+    ddp_worker's too."""
     if grad_dtype not in ("f32", "bf16"):
         raise ValueError(f"grad_dtype {grad_dtype!r}: 'f32' or 'bf16'")
+    if (max_grad_norm is not None or lars is not None) and not fused:
+        raise ValueError("max_grad_norm and lars need fused=True")
+    max_grad_norm = None if max_grad_norm is None else float(max_grad_norm)
+    lars = None if lars is None else float(lars)
     from ..isolation.local import LocalGPUShare
 
     shares, procs = [], []
@@ -201,7 +211,8 @@ def launch_gang(ranks: int = 2, share_gpu: bool = False, steps: int = 10,
                 [sys.executable, "-c",
                  "from kubeshare_amd.parallel.ddp import ddp_worker; "
                  f"ddp_worker({model!r}, {batch}, {image_size}, {steps}, "
-                 f"fused={bool(fused)}, grad_dtype={grad_dtype!r})"],
+                 f"fused={bool(fused)}, grad_dtype={grad_dtype!r}, "
+                 f"max_grad_norm={max_grad_norm!r}, lars={lars!r})"],
                 env=env, cwd=_REPO))
         deadline = time.time() + timeout
         for p in procs:

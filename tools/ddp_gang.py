@@ -11,6 +11,8 @@ server-side quota stats.
     python tools/ddp_gang.py --ranks 2               # 1 rank/GPU
     python tools/ddp_gang.py --ranks 2 --share-gpu --fused [--grad-dtype bf16]
                                                      # gang on the fused path
+    python tools/ddp_gang.py --ranks 2 --share-gpu --fused --clip-grad-norm 1 \
+        --lars 0.001                                 # ... clipped, with LARS
 """
 import argparse
 import json
@@ -38,7 +40,16 @@ def main():
                          "DDP wrapper (default: stock modules under DDP)")
     ap.add_argument("--grad-dtype", choices=("f32", "bf16"), default="f32",
                     help="dtype of the all-reduced bucket (with --fused)")
+    ap.add_argument("--clip-grad-norm", type=float, default=None,
+                    metavar="F", help="clip the averaged gradient to global "
+                    "L2 norm F in the fused step (with --fused)")
+    ap.add_argument("--lars", type=float, default=None, metavar="ETA",
+                    help="layer-wise trust ratio with coefficient ETA in "
+                         "the fused step (with --fused)")
     args = ap.parse_args()
+    if (args.clip_grad_norm is not None or args.lars is not None) \
+            and not args.fused:
+        ap.error("--clip-grad-norm and --lars need --fused")
 
     from kubeshare_amd.parallel import launch_gang
     ok, stats = launch_gang(ranks=args.ranks, share_gpu=args.share_gpu,
@@ -46,7 +57,9 @@ def main():
                             batch=args.batch, image_size=args.image_size,
                             timeout=args.timeout,
                             master_port=args.master_port, fused=args.fused,
-                            grad_dtype=args.grad_dtype)
+                            grad_dtype=args.grad_dtype,
+                            max_grad_norm=args.clip_grad_norm,
+                            lars=args.lars)
     for st in stats:
         print("SCHD_STATS " + json.dumps(st), flush=True)
     print("GANG_OK" if ok else "GANG_FAILED", flush=True)
