@@ -15,7 +15,10 @@ backward issues the weight gradient on a side stream. The staged
 weight's CastWeightsFn node is downstream of every such gradient and
 joins the side stream before it reads them. Where ops.fuse_model has
 flagged the conv (_dgrad_fwd) the staged weight comes with its mirror,
-and conv2d_split runs the data gradient as a forward convolution."""
+and conv2d_split runs the data gradient as a forward convolution. Under
+KUBESHARE_WRW_GEMM=1 (read at each forward) a stride-1 1x1 conv asks
+conv2d_split for the deterministic MFMA weight gradient
+(ops.wrw_gemm_supported, wgrad_gemm=True)."""
 import torch
 import torch.nn as nn
 
@@ -60,6 +63,8 @@ class LowpConv2d(nn.Conv2d):
         if xs is None:
             return self._conv_forward(x, w, self.bias)
         from .. import ops
+        gemm = ops.wrw_gemm_enabled() and ops.wrw_gemm_supported(
+            xs, w, self.stride, self.padding, self.dilation, self.groups)
         return ops.conv2d_split(xs, w, self.stride, self.padding,
                                 self.dilation, self.groups,
-                                self._lowp_mirror)
+                                self._lowp_mirror, gemm)

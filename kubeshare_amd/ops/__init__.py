@@ -21,7 +21,8 @@ _SRCS = [os.path.join(_HERE, "hip", "ks_ops.hip"),
          os.path.join(_HERE, "hip", "cast.hip"),
          os.path.join(_HERE, "hip", "conv_split.hip"),
          os.path.join(_HERE, "hip", "grad_bucket.hip"),
-         os.path.join(_HERE, "hip", "grad_norm.hip")]
+         os.path.join(_HERE, "hip", "grad_norm.hip"),
+         os.path.join(_HERE, "hip", "wrw_gemm.hip")]
 
 _ext = None
 
@@ -957,7 +958,7 @@ def wrw_stream_enabled() -> bool:
 
 
 def conv2d_split(x, w, stride=(1, 1), padding=(0, 0), dilation=(1, 1),
-                 groups=1, mirror=None):
+                 groups=1, mirror=None, wgrad_gemm=False):
     """Bias-free F.conv2d(x, w, None, stride, padding, dilation, groups)
     for CUDA tensors through hip/conv_split.hip: same ATen entry, same
     MIOpen kernels, same values, but the backward issues the weight
@@ -976,11 +977,62 @@ def conv2d_split(x, w, stride=(1, 1), padding=(0, 0), dilation=(1, 1),
     convolution of dy with it, where MIOpen's forward kernels beat its
     data-gradient kernels, instead of convolution_backward's data half.
     Accepted only for bf16, stride 1, dilation 1, groups 1 and a 1x1 or
-    3x3 kernel with "same" padding; anything else raises."""
+    3x3 kernel with "same" padding; anything else raises.
+
+    wgrad_gemm: the backward computes dW with wrw_gemm_1x1
+    (hip/wrw_gemm.hip) instead of MIOpen's weight-gradient solver, in
+    the same place (side stream, or the current one inside a capture):
+    same bits on every run, and no zero fill or cast around it. Accepted
+    only where wrw_gemm_supported holds; anything else raises."""
     def two(v):
         return [int(v), int(v)] if isinstance(v, int) else [int(i) for i in v]
     return _load().conv2d_split(x, w, two(stride), two(padding),
-                                two(dilation), int(groups), mirror)
+                                two(dilation), int(groups), mirror,
+                                bool(wgrad_gemm))
+
+
+# ------------------- 1x1 weight gradients as a deterministic MFMA GEMM
+def wrw_gemm_enabled() -> bool:
+    """KUBESHARE_WRW_GEMM=1 makes every models.conv.LowpConv2d that
+    wrw_gemm_supported accepts compute its weight gradient with
+    wrw_gemm_1x1 (conv2d_split(wgrad_gemm=True)). Off by default: dW then
+    differs from MIOpen's in the last bits (another summation order)."""
+    return os.environ.get("KUBESHARE_WRW_GEMM", "0") == "1"
+
+
+def wrw_gemm_supported(x, w, stride=(1, 1), padding=(0, 0), dilation=(1, 1),
+                       groups=1) -> bool:
+    """True when conv2d_split(x, w, ..., wgrad_gemm=True) is accepted:
+    bf16 CUDA x (N,C,H,W) and w (K,C,1,1) on one device, stride 1, no
+    padding, dilation 1, groups 1, C and K multiples of 8 in [8, 2048]
+    and at least one pixel."""
+    import torch
+
+    def ones(v, want):
+        return (v == want if isinstance(v, int)
+                else tuple(v) == (want, want))
+
+    if x.dim() != 4 or w.dim() != 4 or not (x.is_cuda and w.is_cuda):
+        return False
+    if x.dtype != torch.bfloat16 or w.dtype != torch.bfloat16 \
+            or x.device != w.device:
+        return False
+    if not (ones(stride, 1) and ones(padding, 0) and ones(dilation, 1)
+            and groups == 1 and tuple(w.shape[2:]) == (1, 1)):
+        return False
+    k, c = w.shape[0], w.shape[1]
+    return (x.shape[1] == c and x.numel() > 0
+            and all(n % 8 == 0 and 8 <= n <= 2048 for n in (c, k)))
+
+
+def wrw_gemm_1x1(x, dy):
+    """dW (K,C,1,1), bf16, of a stride-1 1x1 convolution from dense
+    channels-last bf16 CUDA x (N,C,H,W) and dy (N,K,H,W):
+    dW[k,c] = sum over the pixels of dy[.,k] * x[.,c], by hip/wrw_gemm.hip
+    (split-K bf16 MFMA with f32 accumulation, partials added in a fixed
+    order, one rounding): two calls return the same bits. Anything it
+    does not cover raises."""
+    return _load().wrw_gemm_1x1(x, dy)
 
 
 def mirror_weights(weights):

@@ -33,6 +33,11 @@
 // and MIOpen's tuned forward kernels are faster than its data-gradient
 // kernels on these shapes ("Stride-1 data gradients as
 // forward convolutions"). The weight half and everything above stay.
+//
+// With wgrad_gemm the weight half of a stride-1 1x1 convolution is
+// wrw_gemm_1x1 (wrw_gemm.hip) instead of MIOpen's: a deterministic
+// split-K MFMA GEMM without the zero fill and the cast. It runs where the
+// weight half runs, under the same guard, events and record_stream calls.
 #include <torch/extension.h>
 #include <ATen/cuda/CUDAContext.h>
 #include <ATen/cuda/CUDAEvent.h>
@@ -44,6 +49,9 @@
 #include <memory>
 #include <mutex>
 #include <vector>
+
+torch::Tensor wrw_gemm_1x1(torch::Tensor x, torch::Tensor dy);
+bool wrw_gemm_channels_ok(int64_t c, int64_t k);
 
 namespace {
 
@@ -91,7 +99,8 @@ struct Conv2dSplitFn : public torch::autograd::Function<Conv2dSplitFn> {
                                std::vector<int64_t> stride,
                                std::vector<int64_t> padding,
                                std::vector<int64_t> dilation, int64_t groups,
-                               c10::optional<torch::Tensor> mirror) {
+                               c10::optional<torch::Tensor> mirror,
+                               bool wgrad_gemm) {
     TORCH_CHECK(x.is_cuda() && w.is_cuda() && x.dim() == 4 && w.dim() == 4,
                 "conv2d_split: 4-d CUDA tensors expected");
     TORCH_CHECK(x.get_device() == w.get_device(),
@@ -128,7 +137,24 @@ struct Conv2dSplitFn : public torch::autograd::Function<Conv2dSplitFn> {
     } else {
       ctx->save_for_backward({x, w});
     }
+    if (wgrad_gemm) {
+      // dW as a GEMM over the pixels: only these convolutions
+      TORCH_CHECK(stride[0] == 1 && stride[1] == 1 && padding[0] == 0 &&
+                      padding[1] == 0 && dilation[0] == 1 &&
+                      dilation[1] == 1 && groups == 1 && w.size(2) == 1 &&
+                      w.size(3) == 1,
+                  "conv2d_split: wgrad_gemm needs a 1x1 kernel, stride 1, "
+                  "no padding, dilation 1 and groups 1");
+      TORCH_CHECK(x.scalar_type() == at::kBFloat16 &&
+                      w.scalar_type() == at::kBFloat16,
+                  "conv2d_split: wgrad_gemm needs bf16 x and w");
+      TORCH_CHECK(x.size(1) == w.size(1) &&
+                      wrw_gemm_channels_ok(w.size(1), w.size(0)),
+                  "conv2d_split: wgrad_gemm needs channel counts that are "
+                  "multiples of 8 in [8, 2048]");
+    }
     ctx->saved_data["routed"] = routed;
+    ctx->saved_data["wgrad_gemm"] = wgrad_gemm;
     ctx->saved_data["stride"] = stride;
     ctx->saved_data["padding"] = padding;
     ctx->saved_data["dilation"] = dilation;
@@ -155,7 +181,7 @@ struct Conv2dSplitFn : public torch::autograd::Function<Conv2dSplitFn> {
     const auto dilation = ctx->saved_data["dilation"].toIntVector();
     const int64_t groups = ctx->saved_data["groups"].toInt();
     torch::Tensor dx, dw;
-    const torch::autograd::variable_list none(7);
+    const torch::autograd::variable_list none(8);
     if (!dy.defined()) return none;
     const bool need_dx = ctx->needs_input_grad(0);
     const bool need_dw = ctx->needs_input_grad(1);
@@ -166,6 +192,16 @@ struct Conv2dSplitFn : public torch::autograd::Function<Conv2dSplitFn> {
           {data, !data, false});
       return data ? std::get<0>(out) : std::get<1>(out);
     };
+    // the weight half: MIOpen's, or the MFMA GEMM over channels-last x, dy
+    const bool gemm = ctx->saved_data["wgrad_gemm"].toBool();
+    auto cl = [](const torch::Tensor& t) {
+      return t.is_contiguous(at::MemoryFormat::ChannelsLast)
+                 ? t
+                 : t.contiguous(at::MemoryFormat::ChannelsLast);
+    };
+    auto weight_half = [&]() {
+      return gemm ? wrw_gemm_1x1(cl(x), cl(dy)) : half(false);
+    };
     // the data half: with a mirrored weight, the forward convolution of
     // dy with it ("same" padding: R-1-p == p); dW is half(false) either way
     const bool routed = ctx->saved_data["routed"].toBool();
@@ -174,20 +210,16 @@ struct Conv2dSplitFn : public torch::autograd::Function<Conv2dSplitFn> {
       const torch::Tensor& wm = saved[2];
       const int64_t ph = wm.size(2) - 1 - padding[0];
       const int64_t pw = wm.size(3) - 1 - padding[1];
-      const torch::Tensor g =
-          dy.is_contiguous(at::MemoryFormat::ChannelsLast)
-              ? dy
-              : dy.contiguous(at::MemoryFormat::ChannelsLast);
-      return at::convolution(g, wm, c10::nullopt, {1, 1}, {ph, pw}, {1, 1},
-                             /*transposed=*/false, /*output_padding=*/{0, 0},
-                             1);
+      return at::convolution(cl(dy), wm, c10::nullopt, {1, 1}, {ph, pw},
+                             {1, 1}, /*transposed=*/false,
+                             /*output_padding=*/{0, 0}, 1);
     };
     const c10::DeviceIndex dev = (c10::DeviceIndex)dy.get_device();
     c10::cuda::CUDAGuard device_guard(dev);
     if (!need_dw || capturing()) {
       if (need_dx) dx = data_half();
-      if (need_dw) dw = half(false);
-      return {dx, dw, none[2], none[3], none[4], none[5], none[6]};
+      if (need_dw) dw = weight_half();
+      return {dx, dw, none[2], none[3], none[4], none[5], none[6], none[7]};
     }
     const auto cur = c10::cuda::getCurrentCUDAStream(dev);
     std::lock_guard<std::mutex> lock(g_mu);
@@ -202,12 +234,12 @@ struct Conv2dSplitFn : public torch::autograd::Function<Conv2dSplitFn> {
     x.record_stream(side);
     {
       c10::cuda::CUDAStreamGuard stream_guard(side);
-      dw = half(false);
+      dw = weight_half();
     }
     dw.record_stream(cur);
     s.done->record(side);
     s.pending = true;
-    return {dx, dw, none[2], none[3], none[4], none[5], none[6]};
+    return {dx, dw, none[2], none[3], none[4], none[5], none[6], none[7]};
   }
 };
 
@@ -215,9 +247,10 @@ torch::Tensor conv2d_split(torch::Tensor x, torch::Tensor w,
                            std::vector<int64_t> stride,
                            std::vector<int64_t> padding,
                            std::vector<int64_t> dilation, int64_t groups,
-                           c10::optional<torch::Tensor> mirror) {
+                           c10::optional<torch::Tensor> mirror,
+                           bool wgrad_gemm) {
   return Conv2dSplitFn::apply(x, w, stride, padding, dilation, groups,
-                              mirror);
+                              mirror, wgrad_gemm);
 }
 
 // Makes the current stream of every device with a pending weight

@@ -28,6 +28,8 @@
 //    ReLU in one op; the downsample BN's output is never written.
 //  - bias_relu.hip: bias+ReLU(+max-pool) for conv layers without a BN
 //    (the plain VGG16), bias gradient in the same backward pass.
+//  - wrw_gemm.hip: the weight gradient of a stride-1 1x1 convolution as
+//    a deterministic split-K bf16 MFMA GEMM (conv2d_split(wgrad_gemm=)).
 #include <hip/hip_runtime.h>
 #include <torch/extension.h>
 #include <ATen/cuda/CUDAContext.h>
@@ -632,9 +634,15 @@ torch::Tensor conv2d_split(torch::Tensor x, torch::Tensor w,
                            std::vector<int64_t> stride,
                            std::vector<int64_t> padding,
                            std::vector<int64_t> dilation, int64_t groups,
-                           c10::optional<torch::Tensor> mirror);
+                           c10::optional<torch::Tensor> mirror,
+                           bool wgrad_gemm);
 void wgrad_join();
 bool wgrad_pending();
+
+// deterministic split-K bf16 MFMA weight gradient of a stride-1 1x1
+// convolution (wrw_gemm.hip)
+torch::Tensor wrw_gemm_1x1(torch::Tensor x, torch::Tensor dy);
+std::vector<int64_t> wrw_gemm_plan(int64_t P, int64_t C, int64_t K);
 
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("burn", &burn, "occupy the GPU for ~ms milliseconds",
@@ -740,9 +748,19 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("conv2d_split", &conv2d_split, py::arg("x"), py::arg("w"),
         py::arg("stride"), py::arg("padding"), py::arg("dilation"),
         py::arg("groups"), py::arg("mirror") = py::none(),
+        py::arg("wgrad_gemm") = false,
         "bias-free at::convolution; its backward runs the weight gradient "
         "on a side stream (join with wgrad_join) and, given the mirrored "
-        "weight, the data gradient as a forward convolution");
+        "weight, the data gradient as a forward convolution; with "
+        "wgrad_gemm the weight gradient is wrw_gemm_1x1");
+  m.def("wrw_gemm_1x1", &wrw_gemm_1x1, py::arg("x"), py::arg("dy"),
+        "bf16 dW (K,C,1,1) of a stride-1 1x1 convolution from channels-last "
+        "bf16 x (N,C,H,W) and dy (N,K,H,W): split-K MFMA GEMM, no atomics, "
+        "same bits on every run");
+  m.def("wrw_gemm_plan", &wrw_gemm_plan, py::arg("P"), py::arg("C"),
+        py::arg("K"),
+        "{TM, TN, S, L}: tile rows and columns, slices and pixels per "
+        "slice that wrw_gemm_1x1 uses for P pixels, C -> K channels");
   m.def("wgrad_join", &wgrad_join,
         "the current stream waits for every pending side-stream weight "
         "gradient; a no-op with nothing pending");
