@@ -18,7 +18,9 @@ flagged the conv (_dgrad_fwd) the staged weight comes with its mirror,
 and conv2d_split runs the data gradient as a forward convolution. Under
 KUBESHARE_WRW_GEMM=1 (read at each forward) a stride-1 1x1 conv asks
 conv2d_split for the deterministic MFMA weight gradient
-(ops.wrw_gemm_supported, wgrad_gemm=True)."""
+(ops.wrw_gemm_supported, wgrad_gemm=True); under KUBESHARE_WRW_GEMM=all
+every 1x1 and 3x3 conv of stride 1 or 2 that ops.wrw_gemm_conv_supported
+accepts asks for it (wgrad_gemm="conv"), for ResNet50 all but the stem."""
 import torch
 import torch.nn as nn
 
@@ -63,8 +65,12 @@ class LowpConv2d(nn.Conv2d):
         if xs is None:
             return self._conv_forward(x, w, self.bias)
         from .. import ops
-        gemm = ops.wrw_gemm_enabled() and ops.wrw_gemm_supported(
-            xs, w, self.stride, self.padding, self.dilation, self.groups)
+        mode = ops.wrw_gemm_mode()
+        args = (xs, w, self.stride, self.padding, self.dilation, self.groups)
+        if mode == "all":
+            gemm = "conv" if ops.wrw_gemm_conv_supported(*args) else False
+        else:
+            gemm = mode == "1" and ops.wrw_gemm_supported(*args)
         return ops.conv2d_split(xs, w, self.stride, self.padding,
                                 self.dilation, self.groups,
                                 self._lowp_mirror, gemm)

@@ -983,12 +983,21 @@ def conv2d_split(x, w, stride=(1, 1), padding=(0, 0), dilation=(1, 1),
     (hip/wrw_gemm.hip) instead of MIOpen's weight-gradient solver, in
     the same place (side stream, or the current one inside a capture):
     same bits on every run, and no zero fill or cast around it. Accepted
-    only where wrw_gemm_supported holds; anything else raises."""
+    only where wrw_gemm_supported holds; anything else raises.
+    wgrad_gemm="conv" asks for wrw_gemm_conv instead, which also covers
+    3x3 kernels with padding 1 and stride 2: accepted only where
+    wrw_gemm_conv_supported holds; anything else raises."""
     def two(v):
         return [int(v), int(v)] if isinstance(v, int) else [int(i) for i in v]
+    if isinstance(wgrad_gemm, str):
+        if wgrad_gemm != "conv":
+            raise ValueError(f"conv2d_split: wgrad_gemm={wgrad_gemm!r}: "
+                             "False, True or \"conv\" expected")
+        mode = 2
+    else:
+        mode = int(bool(wgrad_gemm))
     return _load().conv2d_split(x, w, two(stride), two(padding),
-                                two(dilation), int(groups), mirror,
-                                bool(wgrad_gemm))
+                                two(dilation), int(groups), mirror, mode)
 
 
 # ------------------- 1x1 weight gradients as a deterministic MFMA GEMM
@@ -996,8 +1005,20 @@ def wrw_gemm_enabled() -> bool:
     """KUBESHARE_WRW_GEMM=1 makes every models.conv.LowpConv2d that
     wrw_gemm_supported accepts compute its weight gradient with
     wrw_gemm_1x1 (conv2d_split(wgrad_gemm=True)). Off by default: dW then
-    differs from MIOpen's in the last bits (another summation order)."""
-    return os.environ.get("KUBESHARE_WRW_GEMM", "0") == "1"
+    differs from MIOpen's in the last bits (another summation order).
+    True for `1` and for `all` (wrw_gemm_mode)."""
+    return wrw_gemm_mode() != "0"
+
+
+def wrw_gemm_mode() -> str:
+    """KUBESHARE_WRW_GEMM as `0`, `1` or `all`. `1` routes the stride-1
+    1x1 convs (wrw_gemm_supported, wgrad_gemm=True); `all` routes every
+    LowpConv2d that wrw_gemm_conv_supported accepts through
+    conv2d_split(wgrad_gemm="conv"): the 1x1 and 3x3 convs of stride 1
+    and 2, for ResNet50 all but the stem. Anything else, and unset, is
+    `0`."""
+    v = os.environ.get("KUBESHARE_WRW_GEMM", "0")
+    return v if v in ("1", "all") else "0"
 
 
 def wrw_gemm_supported(x, w, stride=(1, 1), padding=(0, 0), dilation=(1, 1),
@@ -1033,6 +1054,53 @@ def wrw_gemm_1x1(x, dy):
     order, one rounding): two calls return the same bits. Anything it
     does not cover raises."""
     return _load().wrw_gemm_1x1(x, dy)
+
+
+_WRW_CONV_CONFIGS = ((1, 1, 0), (3, 1, 1), (1, 2, 0), (3, 2, 1))  # (k, st, p)
+
+
+def wrw_gemm_conv_supported(x, w, stride=(1, 1), padding=(0, 0),
+                            dilation=(1, 1), groups=1) -> bool:
+    """True when conv2d_split(x, w, ..., wgrad_gemm="conv") is accepted:
+    bf16 CUDA x (N,C,H,W) and w (K,C,k,k) on one device, (k, stride,
+    padding) one of (1,1,0), (3,1,1), (1,2,0), (3,2,1), dilation 1,
+    groups 1, C and K multiples of 8 in [8, 2048], at least one pixel and
+    N*H*W below 2**31 (pixel indices are 32-bit)."""
+    import torch
+
+    def same(v):
+        if isinstance(v, int):
+            return v
+        v = tuple(v)
+        return v[0] if len(v) == 2 and v[0] == v[1] else None
+
+    if x.dim() != 4 or w.dim() != 4 or not (x.is_cuda and w.is_cuda):
+        return False
+    if x.dtype != torch.bfloat16 or w.dtype != torch.bfloat16 \
+            or x.device != w.device:
+        return False
+    cfg = (same(w.shape[2:]), same(stride), same(padding))
+    if cfg not in _WRW_CONV_CONFIGS or same(dilation) != 1 or groups != 1:
+        return False
+    k, c = w.shape[0], w.shape[1]
+    return (x.shape[1] == c and 0 < x.numel() // c < 2 ** 31
+            and all(n % 8 == 0 and 8 <= n <= 2048 for n in (c, k)))
+
+
+def wrw_gemm_conv(x, dy, kernel_size, stride=1, padding=0):
+    """dW (K,C,k,k), bf16, dense channels-last, of a k x k convolution
+    with (k, stride, padding) one of (1,1,0), (3,1,1), (1,2,0), (3,2,1),
+    dilation 1 and groups 1, from dense channels-last bf16 CUDA x
+    (N,C,H,W) and dy (N,K,Ho,Wo):
+    dW[k,c,r,s] = sum over n, ho, wo of
+                  dy[n,k,ho,wo] * x[n,c,ho*stride+r-p,wo*stride+s-p]
+    with zeros outside the image, by hip/wrw_gemm.hip's implicit GEMM
+    (the engine of wrw_gemm_1x1 with a gathered x operand; f32
+    accumulation, partials added in a fixed order, one rounding): two
+    calls return the same bits. For (1,1,0) it is wrw_gemm_1x1. Anything
+    it does not cover raises."""
+    return _load().wrw_gemm_conv(x, dy, int(kernel_size), int(stride),
+                                 int(padding))
 
 
 def mirror_weights(weights):

@@ -38,6 +38,9 @@
 // wrw_gemm_1x1 (wrw_gemm.hip) instead of MIOpen's: a deterministic
 // split-K MFMA GEMM without the zero fill and the cast. It runs where the
 // weight half runs, under the same guard, events and record_stream calls.
+// wgrad_gemm is 0 (stock), 1 (that) or 2 ("conv" in Python): with 2 the
+// weight half is wrw_gemm_conv, which also covers 3x3 kernels with
+// padding 1 and stride 2.
 #include <torch/extension.h>
 #include <ATen/cuda/CUDAContext.h>
 #include <ATen/cuda/CUDAEvent.h>
@@ -52,6 +55,9 @@
 
 torch::Tensor wrw_gemm_1x1(torch::Tensor x, torch::Tensor dy);
 bool wrw_gemm_channels_ok(int64_t c, int64_t k);
+torch::Tensor wrw_gemm_conv(torch::Tensor x, torch::Tensor dy, int64_t kernel,
+                            int64_t stride, int64_t padding);
+bool wrw_gemm_conv_geometry_ok(int64_t k, int64_t st, int64_t p);
 
 namespace {
 
@@ -100,7 +106,9 @@ struct Conv2dSplitFn : public torch::autograd::Function<Conv2dSplitFn> {
                                std::vector<int64_t> padding,
                                std::vector<int64_t> dilation, int64_t groups,
                                c10::optional<torch::Tensor> mirror,
-                               bool wgrad_gemm) {
+                               int64_t wgrad_gemm) {
+    TORCH_CHECK(wgrad_gemm >= 0 && wgrad_gemm <= 2,
+                "conv2d_split: wgrad_gemm is 0, 1 or 2");
     TORCH_CHECK(x.is_cuda() && w.is_cuda() && x.dim() == 4 && w.dim() == 4,
                 "conv2d_split: 4-d CUDA tensors expected");
     TORCH_CHECK(x.get_device() == w.get_device(),
@@ -139,12 +147,24 @@ struct Conv2dSplitFn : public torch::autograd::Function<Conv2dSplitFn> {
     }
     if (wgrad_gemm) {
       // dW as a GEMM over the pixels: only these convolutions
-      TORCH_CHECK(stride[0] == 1 && stride[1] == 1 && padding[0] == 0 &&
-                      padding[1] == 0 && dilation[0] == 1 &&
-                      dilation[1] == 1 && groups == 1 && w.size(2) == 1 &&
-                      w.size(3) == 1,
-                  "conv2d_split: wgrad_gemm needs a 1x1 kernel, stride 1, "
-                  "no padding, dilation 1 and groups 1");
+      if (wgrad_gemm == 1) {
+        TORCH_CHECK(stride[0] == 1 && stride[1] == 1 && padding[0] == 0 &&
+                        padding[1] == 0 && dilation[0] == 1 &&
+                        dilation[1] == 1 && groups == 1 && w.size(2) == 1 &&
+                        w.size(3) == 1,
+                    "conv2d_split: wgrad_gemm needs a 1x1 kernel, stride 1, "
+                    "no padding, dilation 1 and groups 1");
+      } else {
+        TORCH_CHECK(w.size(2) == w.size(3) && stride[0] == stride[1] &&
+                        padding[0] == padding[1] &&
+                        wrw_gemm_conv_geometry_ok(w.size(2), stride[0],
+                                                  padding[0]) &&
+                        dilation[0] == 1 && dilation[1] == 1 && groups == 1 &&
+                        x.numel() > 0 && x.numel() / x.size(1) < (1LL << 31),
+                    "conv2d_split: wgrad_gemm=\"conv\" needs (kernel, "
+                    "stride, padding) in (1,1,0), (3,1,1), (1,2,0), (3,2,1), "
+                    "dilation 1, groups 1 and 1 <= N*H*W < 2^31");
+      }
       TORCH_CHECK(x.scalar_type() == at::kBFloat16 &&
                       w.scalar_type() == at::kBFloat16,
                   "conv2d_split: wgrad_gemm needs bf16 x and w");
@@ -193,13 +213,15 @@ struct Conv2dSplitFn : public torch::autograd::Function<Conv2dSplitFn> {
       return data ? std::get<0>(out) : std::get<1>(out);
     };
     // the weight half: MIOpen's, or the MFMA GEMM over channels-last x, dy
-    const bool gemm = ctx->saved_data["wgrad_gemm"].toBool();
+    const int64_t gemm = ctx->saved_data["wgrad_gemm"].toInt();
     auto cl = [](const torch::Tensor& t) {
       return t.is_contiguous(at::MemoryFormat::ChannelsLast)
                  ? t
                  : t.contiguous(at::MemoryFormat::ChannelsLast);
     };
     auto weight_half = [&]() {
+      if (gemm == 2)
+        return wrw_gemm_conv(cl(x), cl(dy), w.size(2), stride[0], padding[0]);
       return gemm ? wrw_gemm_1x1(cl(x), cl(dy)) : half(false);
     };
     // the data half: with a mirrored weight, the forward convolution of
@@ -248,7 +270,7 @@ torch::Tensor conv2d_split(torch::Tensor x, torch::Tensor w,
                            std::vector<int64_t> padding,
                            std::vector<int64_t> dilation, int64_t groups,
                            c10::optional<torch::Tensor> mirror,
-                           bool wgrad_gemm) {
+                           int64_t wgrad_gemm) {
   return Conv2dSplitFn::apply(x, w, stride, padding, dilation, groups,
                               mirror, wgrad_gemm);
 }

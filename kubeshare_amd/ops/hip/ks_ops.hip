@@ -29,7 +29,9 @@
 //  - bias_relu.hip: bias+ReLU(+max-pool) for conv layers without a BN
 //    (the plain VGG16), bias gradient in the same backward pass.
 //  - wrw_gemm.hip: the weight gradient of a stride-1 1x1 convolution as
-//    a deterministic split-K bf16 MFMA GEMM (conv2d_split(wgrad_gemm=)).
+//    a deterministic split-K bf16 MFMA GEMM (conv2d_split(wgrad_gemm=)),
+//    and of 3x3 and stride-2 convolutions as an implicit GEMM on the same
+//    engine (wrw_gemm_conv, wgrad_gemm=2).
 #include <hip/hip_runtime.h>
 #include <torch/extension.h>
 #include <ATen/cuda/CUDAContext.h>
@@ -635,14 +637,17 @@ torch::Tensor conv2d_split(torch::Tensor x, torch::Tensor w,
                            std::vector<int64_t> padding,
                            std::vector<int64_t> dilation, int64_t groups,
                            c10::optional<torch::Tensor> mirror,
-                           bool wgrad_gemm);
+                           int64_t wgrad_gemm);
 void wgrad_join();
 bool wgrad_pending();
 
 // deterministic split-K bf16 MFMA weight gradient of a stride-1 1x1
 // convolution (wrw_gemm.hip)
 torch::Tensor wrw_gemm_1x1(torch::Tensor x, torch::Tensor dy);
-std::vector<int64_t> wrw_gemm_plan(int64_t P, int64_t C, int64_t K);
+std::vector<int64_t> wrw_gemm_plan(int64_t P, int64_t C, int64_t K,
+                                   int64_t taps);
+torch::Tensor wrw_gemm_conv(torch::Tensor x, torch::Tensor dy, int64_t kernel,
+                            int64_t stride, int64_t padding);
 
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("burn", &burn, "occupy the GPU for ~ms milliseconds",
@@ -748,19 +753,27 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("conv2d_split", &conv2d_split, py::arg("x"), py::arg("w"),
         py::arg("stride"), py::arg("padding"), py::arg("dilation"),
         py::arg("groups"), py::arg("mirror") = py::none(),
-        py::arg("wgrad_gemm") = false,
+        py::arg("wgrad_gemm") = 0,
         "bias-free at::convolution; its backward runs the weight gradient "
         "on a side stream (join with wgrad_join) and, given the mirrored "
         "weight, the data gradient as a forward convolution; with "
-        "wgrad_gemm the weight gradient is wrw_gemm_1x1");
+        "wgrad_gemm 1 (or True) the weight gradient is wrw_gemm_1x1, with "
+        "2 wrw_gemm_conv");
   m.def("wrw_gemm_1x1", &wrw_gemm_1x1, py::arg("x"), py::arg("dy"),
         "bf16 dW (K,C,1,1) of a stride-1 1x1 convolution from channels-last "
         "bf16 x (N,C,H,W) and dy (N,K,H,W): split-K MFMA GEMM, no atomics, "
         "same bits on every run");
   m.def("wrw_gemm_plan", &wrw_gemm_plan, py::arg("P"), py::arg("C"),
-        py::arg("K"),
+        py::arg("K"), py::arg("taps") = 1,
         "{TM, TN, S, L}: tile rows and columns, slices and pixels per "
-        "slice that wrw_gemm_1x1 uses for P pixels, C -> K channels");
+        "slice that wrw_gemm_1x1 uses for P pixels, C -> K channels, or "
+        "wrw_gemm_conv for P output pixels and a kernel of `taps` taps");
+  m.def("wrw_gemm_conv", &wrw_gemm_conv, py::arg("x"), py::arg("dy"),
+        py::arg("kernel"), py::arg("stride"), py::arg("padding"),
+        "bf16 dW (K,C,k,k), channels-last, of a k x k convolution, (k, "
+        "stride, padding) in (1,1,0), (3,1,1), (1,2,0), (3,2,1), from "
+        "channels-last bf16 x (N,C,H,W) and dy (N,K,Ho,Wo): implicit "
+        "split-K MFMA GEMM, no atomics, same bits on every run");
   m.def("wgrad_join", &wgrad_join,
         "the current stream waits for every pending side-stream weight "
         "gradient; a no-op with nothing pending");

@@ -17,7 +17,13 @@ other's fastest, else `tie`. `plan` is {TM, TN, S, L} of the GEMM;
 `*_err_over_bound` is each result's largest error against a float64
 reference over the elementwise bound of tests/test_wrw_gemm_gpu.py (one
 bf16 rounding plus the worst case of an f32 accumulation), at the timed
-size."""
+size.
+
+--shapes conv (or all) adds the ten other distinct conv shapes of ResNet50
+but the stem, 3x3 at stride 1 and 2 and 1x1 at stride 2, for which the
+GEMM side is ops.wrw_gemm_conv (the same engine with a gathered x operand)
+and the bound is that of tests/test_wrw_gemm_conv_gpu.py; the committed
+record of those rows is profiles/wrw_gemm_conv_bench.json."""
 import argparse
 import json
 import os
@@ -34,6 +40,13 @@ SHAPES = [  # (C in, K out, h, weight gradients per ResNet50 step)
     (256, 1024, 14, 6), (1024, 256, 14, 5), (1024, 512, 14, 1),
     (512, 2048, 7, 3), (2048, 512, 7, 2),
 ]
+CONV_SHAPES = [  # (C in, K out, input h, per step, kernel, stride)
+    (64, 64, 56, 3, 3, 1), (128, 128, 28, 3, 3, 1), (256, 256, 14, 5, 3, 1),
+    (512, 512, 7, 2, 3, 1),
+    (128, 128, 56, 1, 3, 2), (256, 256, 28, 1, 3, 2), (512, 512, 14, 1, 3, 2),
+    (256, 512, 56, 1, 1, 2), (512, 1024, 28, 1, 1, 2),
+    (1024, 2048, 14, 1, 1, 2),
+]
 HBM_BYTES_PER_MS = 8e9
 
 
@@ -43,6 +56,9 @@ def main():
     ap.add_argument("--repeats", type=int, default=5)
     ap.add_argument("--window-ms", type=float, default=20.0)
     ap.add_argument("--warmup", type=int, default=5)
+    ap.add_argument("--shapes", choices=("1x1", "conv", "all"),
+                    default="1x1", help="stride-1 1x1 (default), the 3x3 "
+                    "and stride-2 shapes, or both")
     ap.add_argument("--out", default=None, help="also write the lines here")
     args = ap.parse_args()
 
@@ -93,43 +109,63 @@ def main():
                 gpu[key].append(t)
         return gpu
 
+    def weight_grad_f64(x64, dy64, ker, st, pad):
+        """dW (K, C, ker, ker) in float64: one GEMM per tap over the
+        strided window of the zero-padded x that the tap reads."""
+        ho, wo = dy64.shape[2:]
+        xp = torch.nn.functional.pad(x64, (pad, pad, pad, pad))
+        dyr = dy64.permute(1, 0, 2, 3).reshape(dy64.shape[1], -1)
+        taps = [dyr @ xp[:, :, r:r + st * ho:st, s:s + st * wo:st]
+                .permute(0, 2, 3, 1).reshape(-1, x64.shape[1])
+                for r in range(ker) for s in range(ker)]
+        return torch.stack(taps, -1).view(dy64.shape[1], x64.shape[1], ker,
+                                          ker)
+
+    shapes = []
+    if args.shapes in ("1x1", "all"):
+        shapes += [s + (1, 1) for s in SHAPES]
+    if args.shapes in ("conv", "all"):
+        shapes += CONV_SHAPES
     lines = []
     total = {"stock": 0.0, "gemm": 0.0}
     torch.manual_seed(0)
     with torch.no_grad():
-        for c, k, h, per_step in SHAPES:
-            w = rand((k, c, 1, 1))
+        for c, k, h, per_step, ker, st in shapes:
+            pad = ker // 2
+            ho = (h + 2 * pad - ker) // st + 1
+            w = rand((k, c, ker, ker))
             x = rand((args.batch, c, h, h))
-            dy = rand((args.batch, k, h, h))
-            pixels = args.batch * h * h
+            dy = rand((args.batch, k, ho, ho))
+            pixels = args.batch * ho * ho  # the reduction length
 
             def stock():
                 return aten.convolution_backward(
-                    dy, x, w, None, [1, 1], [0, 0], [1, 1], False, [0, 0],
-                    1, [False, True, False])[1]
+                    dy, x, w, None, [st, st], [pad, pad], [1, 1], False,
+                    [0, 0], 1, [False, True, False])[1]
 
             def gemm():
-                return ops.wrw_gemm_1x1(x, dy)
+                return ops.wrw_gemm_conv(x, dy, ker, st, pad)
 
             # both results against float64, over the bound of
-            # tests/test_wrw_gemm_gpu.py
-            xr = x.permute(0, 2, 3, 1).reshape(pixels, c).double()
-            dyr = dy.permute(0, 2, 3, 1).reshape(pixels, k).double()
-            ref = dyr.t() @ xr
-            bound = 2.0 ** -8 * ref.abs() + pixels * 2.0 ** -24 * (
-                dyr.abs().t() @ xr.abs())
+            # tests/test_wrw_gemm_gpu.py and tests/test_wrw_gemm_conv_gpu.py
+            ref = weight_grad_f64(x.double(), dy.double(), ker, st, pad)
+            bound = 2.0 ** -8 * ref.abs() + pixels * 2.0 ** -24 * \
+                weight_grad_f64(x.double().abs(), dy.double().abs(), ker, st,
+                                pad)
 
             def over_bound(dw):
-                err = (dw.double().reshape(k, c) - ref).abs()
+                err = (dw.double() - ref).abs()
                 return round((err / bound).max().item(), 4)
 
-            r = {"name": f"{c}->{k} 1x1 @{h}", "batch": args.batch,
+            name = f"{c}->{k} {ker}x{ker} @{h}" + (f"->{ho}" if st > 1 else "")
+            r = {"name": name, "batch": args.batch,
                  "pixels": pixels, "per_step": per_step,
-                 "plan": plan(pixels, c, k),
-                 "min_ms": round(2 * pixels * (c + k) / HBM_BYTES_PER_MS, 4),
+                 "plan": plan(pixels, c, k, ker * ker),
+                 "min_ms": round(2 * (args.batch * h * h * c + pixels * k)
+                                 / HBM_BYTES_PER_MS, 4),
                  "stock_err_over_bound": over_bound(stock()),
                  "gemm_err_over_bound": over_bound(gemm())}
-            del xr, dyr, ref, bound
+            del ref, bound
             gpu = measure({"stock": stock, "gemm": gemm})
             for key, ts in gpu.items():
                 r[key + "_ms"] = round(statistics.median(ts), 4)
@@ -146,7 +182,8 @@ def main():
             del w, x, dy
             torch.cuda.empty_cache()
     line = json.dumps({
-        "name": "ResNet50 step, 33 stride-1 1x1 weight gradients",
+        "name": "ResNet50 step, %d weight gradients (--shapes %s)" % (
+            sum(s[3] for s in shapes), args.shapes),
         "stock_ms_per_step": round(total["stock"], 4),
         "gemm_ms_per_step": round(total["gemm"], 4)})
     print(line, flush=True)
